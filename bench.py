@@ -12,17 +12,23 @@ labels to rank 0 inside the timed region.
 torchrun environment, rendezvous on 127.0.0.1 -- what the reference's scripts/run_pipeline.py:195-206 does with mp.spawn);
 under torchrun (RANK / WORLD_SIZE set) it is one rank.  N ranks on fewer than N devices is an error, never a silent N = 1.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ``--steps`` steps, writes ``--dump-outputs`` if given
+and prints the line; whatever takes runs of its own is measured only with ``--full``.  Extra objects:
   ranks_seen      world size as torch.distributed reports it + the all-gathered device identities of the ranks.
   roofline        the kernel with the longest average launch among the traced ones (the neighbour-search launch, layer-0 and layer-1
                   attention kernels), timed live with HIP events recorded by the library around that kernel's launch on the
                   launch stream; `roofline_other` carries the rest.  MFMA kernels: `frac` prices the flops the kernel
                   EXECUTES, `frac_reference_formulation` the flops of the reference's formulation of the same result.
-  cpu_baseline    the CPU oracle (port of the reference path) on this box's host cores, best of a thread sweep.
-  latency         the model-class API (transform -> batcher -> forward -> update_probs) at the YAMLs' batch sizes 1 and 4:
+                  `avg_launch_ms_alone` (the same kernels with nothing else on the GPU): --full only.
+  cpu_baseline    --full: the CPU oracle (port of the reference path) on this box's host cores, best of a thread sweep.
+  latency         --full: the model-class API (transform -> batcher -> forward -> update_probs) at the YAMLs' batch sizes 1 and 4:
                   per-frame median / p95 over >= 200 frames (N = 1).
-  workloads       BASELINE.json configs[2] / [3] (KPConv Toronto3D, PointPillars KITTI): `bench.py --workload ...` run as a child
-                  process each, after the headline measurement (N = 1).
+  workloads       --full: BASELINE.json configs[2] / [3] (KPConv Toronto3D, PointPillars KITTI): `bench.py --workload ... --full`
+                  run as a child process each, after the headline measurement (N = 1).
+
+``--dump-outputs DIR`` (RandLA-Net inference): after the timed steps, rank 0 writes what the LAST timed step handed its caller --
+``labels.npy`` (the argmax labels [B, N]) and ``logits.npy`` (the scores [B * N, C]; a fixed, seeded sample of rows where the
+whole array would exceed DUMP_LOGIT_ROWS) -- as float32.  Inputs and weights are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -301,6 +307,29 @@ def device_identity(dev):
                                       getattr(pr, "pci_device_id", 0))
 
 
+DUMP_LOGIT_ROWS = 1 << 18      # 2^18 rows x 19 classes x 4 B = 20 MB of the 438 MB logits of a 128-frame step
+DUMP_LABEL_MAX = 1 << 23       # labels as float32: at most 32 MB (all of them up to 186 frames of 45056 points)
+
+
+def _seeded_rows(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k of n rows; None (= all rows) when n <= k."""
+    if n <= k:
+        return None
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(path, scores, labels):
+    """--dump-outputs: the last timed step's scores [B, N, C] and labels [B, N] as DIR/logits.npy ([rows, C]) and DIR/labels.npy
+    (flat), float32; arrays over the caps are replaced by a seeded sample of their rows (seeds 0 / 1), at most 52 MB in all."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr, cap, seed in (("logits", scores.reshape(-1, scores.shape[-1]), DUMP_LOGIT_ROWS, 0),
+                                 ("labels", labels.reshape(-1), DUMP_LABEL_MAX, 1)):
+        idx = _seeded_rows(arr.shape[0], cap, seed)
+        if idx is not None:
+            arr = arr[torch.from_numpy(idx).to(arr.device)]
+        np.save(os.path.join(path, name + ".npy"), arr.float().cpu().numpy())
+
+
 def emit(out):
     """The ONE JSON line, as the LAST line of stdout: RCCL writes its version banner through C stdio, which a pipe or a file buffers until
     the process exits -- i.e. it would land BEHIND a line printed from Python (seen on the MI355X: tools/r06_calls/call_aa.sh).  Everything
@@ -411,9 +440,15 @@ def main():
     ap.add_argument("--no-overlap", action="store_true",
                     help="upload, neighbour pyramid and forward of a batch back to back on one stream instead of the "
                          "three-stream pipeline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the KPConv / PointPillars side measurements")
-    ap.add_argument("--no-latency", action="store_true", help="skip the small-batch (B = 1 / 4) model-API latency measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the traced kernels alone, the CPU baseline, the small-batch "
+                         "latency and the KPConv / PointPillars side workloads (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's logits and labels to DIR/*.npy (float32; RandLA-Net inference)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-workloads", action="store_true", help="with --full: skip the KPConv / PointPillars side measurements")
+    ap.add_argument("--no-latency", action="store_true",
+                    help="with --full: skip the small-batch (B = 1 / 4) model-API latency measurement")
     ap.add_argument("--breakdown", action="store_true", help="also time every kernel once (after the timed region)")
     ap.add_argument("--train", action="store_true",
                     help="SURVEY.md §8 f4: time a DATA-PARALLEL TRAINING step of RandLA-Net instead of inference -- forward + loss + backward "
@@ -423,6 +458,9 @@ def main():
                     help="CPU / gloo dry run of the launcher and of every N > 1 branch with a stand-in for the GPU step "
                          "(tests/test_bench_launcher.py); prints a line marked \"stub\": true that is NOT a measurement")
     args = ap.parse_args()
+    if args.dump_outputs and (args.stub or args.train or args.workload != "randlanet"):
+        raise SystemExit("bench.py: --dump-outputs writes the outputs of the RandLA-Net inference step only "
+                         "(the default --workload, without --stub or --train)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no torchrun around us: be the launcher (N ranks, one per GPU), never a silent single rank
@@ -501,6 +539,7 @@ def main():
         # the frames in reverse order), so consecutive steps never upload / search / classify the same bytes.
         hosts = [torch.from_numpy(frames).pin_memory(), torch.from_numpy(np.ascontiguousarray(frames[::-1])).pin_memory()]
     step_no = [0]
+    last_scores = [None]          # what the latest submit handed back (--dump-outputs)
     gather = mdist.PredictionGather(B, N, CFG["num_classes"], dev)
 
     # Every step ends with the argmax of its scores ("forward + softmax/argmax" per frame) into a uint8 label
@@ -520,6 +559,7 @@ def main():
             # 0.15 ms of label post-processing between consecutive forwards)
             stream.compute_stream.wait_event(labelled[slot])
         scores = stream.submit(hosts[slot], None, knn_trace, fwd_trace, done)
+        last_scores[0] = scores
         step_no[0] += 1
         if post is not None:
             with torch.cuda.stream(post):
@@ -563,6 +603,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the engine: the measurements of --full reuse its score buffers
+        dump_outputs(args.dump_outputs, last_scores[0], gather.labels[(args.warmup + K - 1) % gather.depth])
 
     # N > 1 on the hardware: the first multi-GPU run is also a CORRECTNESS run -- rank 0 recomputes, on the label buffers the RCCL
     # gather delivered for the LAST step, the checksums every rank computed on its own labels (outside the timed region)
@@ -598,21 +641,22 @@ def main():
         # the same three kernels with NOTHING else on the GPU (after the timed region): what the overlap with the other stream
         # costs each of them -- the neighbour-search launch runs under the forward on purpose and takes ~1.5x its solo time there
         alone = {}
-        try:
-            e1 = stream.single_engine()
-            a_ev, b_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a_ev.record(); b_ev.record()
-            torch.cuda.synchronize()
-            for kind, tag in TRACED:
-                ts = []
-                for _ in range(3):
-                    tr = make_trace(tag, a_ev, b_ev)
-                    e1.step(stream.pts[0], stream.pts[0], tr if kind == "knn" else None, tr if kind == "fwd" else None)
-                    torch.cuda.synchronize()
-                    ts.append(a_ev.elapsed_time(b_ev))
-                alone[(kind, tag)] = float(np.median(ts))
-        except Exception:
-            alone = {}
+        if args.full:
+            try:
+                e1 = stream.single_engine()
+                a_ev, b_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a_ev.record(); b_ev.record()
+                torch.cuda.synchronize()
+                for kind, tag in TRACED:
+                    ts = []
+                    for _ in range(3):
+                        tr = make_trace(tag, a_ev, b_ev)
+                        e1.step(stream.pts[0], stream.pts[0], tr if kind == "knn" else None, tr if kind == "fwd" else None)
+                        torch.cuda.synchronize()
+                        ts.append(a_ev.elapsed_time(b_ev))
+                    alone[(kind, tag)] = float(np.median(ts))
+            except Exception:
+                alone = {}
         # per-step intervals on the compute stream (completion of step i-1 -> completion of step i)
         iv = np.array([done_ev[i].elapsed_time(done_ev[i + 1]) for i in range(K)])
         per_tag = {}
@@ -695,7 +739,7 @@ def main():
                 e1.step(pts, pts, make_trace(tg, a, b), None); torch.cuda.synchronize()
                 bd["knn:%d" % tg] = a.elapsed_time(b)
             out["breakdown_ms"] = bd
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             e1 = stream.single_engine()           # labels of the first frames from one more (untimed) pass
             sc = e1.step(stream.pts[0], stream.pts[0])
             torch.cuda.synchronize()
@@ -704,12 +748,12 @@ def main():
             torch.set_num_threads(HOST_THREADS)
         else:
             out["cpu_baseline"] = None
-        if world == 1 and not args.no_latency:
+        if args.full and world == 1 and not args.no_latency:
             try:
                 out["latency"] = latency(dev, sd)
             except Exception as e:          # a side measurement must never take the headline line down
                 out["latency"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_workloads:
+        if args.full and world == 1 and not args.no_workloads:
             # each side workload in its OWN process (`bench.py --workload ...`, what a deployment runs: one process per GPU and
             # model).  In-process after the headline they inherit its five HIP streams' hardware-queue assignments -- ROCm maps
             # streams to queues in first-use order -- and PointPillars' two lanes then share a queue: 1156 instead of 1390-1406
@@ -730,8 +774,7 @@ def main():
                        "--warmup", "30" if name == "kpconv" else "12"]       # (a fresh process: the
                 # first steps still grow the allocator pools of both streams -- with 3 warm-up steps a cold box showed 13 ms outliers
                 # among 8.8 ms steps)
-                if args.no_cpu_baseline:
-                    cmd.append("--no-cpu-baseline")
+                cmd.append("--no-cpu-baseline" if args.no_cpu_baseline else "--full")
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, stdin=subprocess.DEVNULL)
                     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -2,7 +2,7 @@
 
 Same JSON contract as the RandLA-Net line (bench.py): `value` = units/s with inputs resident in HBM, `roofline` for
 the dominant op timed live with HIP events on the launch stream (torch's current stream: these ops are launched
-from Python through the C ABI on it), `cpu_baseline` = the CPU oracle (port of the reference path) on a bounded
+from Python through the C ABI on it), `cpu_baseline` (--full only) = the CPU oracle (port of the reference path) on a bounded
 sample.  Units: KPConv = input spheres (batch build on the GPU + forward), PointPillars = sweeps (voxelize +
 pillar features + backbone + heads).
 """
@@ -410,7 +410,7 @@ def run_pointpillars(args, rank, world, dev, dist):
                    (pm, lane_units, "x".join(str(int(d)) for d in pf_shapes[1].shape)), len(pf_in)),
     ]
     out["roofline_other"] = other
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import pointpillars_ref as P          # the checker, used here only as the timed CPU baseline
         pts = [torch.from_numpy(c) for c in clouds_np[:1]]
         P.forward(sd, cfg, pts)
@@ -643,7 +643,7 @@ def run_kpconv(args, rank, world, dev, dist):
                    "event intervals summed (rotation + count, fill + rotation back): the read-back of the pooled size between them "
                    "is not in the figure" % (sn, sm, 2 * cfg['first_subsampling_dl']), len(prim_in)),
     ]
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import kpconv_ref as K                # the checker, used here only as the timed CPU baseline
         sp = spheres[0]
         feats = torch.ones((len(sp), 1))

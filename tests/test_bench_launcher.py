@@ -92,3 +92,53 @@ def test_more_ranks_than_devices_fails_loudly_on_the_gpu_box():
     n = torch.cuda.device_count()
     r = _run(["--gpus", str(n + 1), "--steps", "1", "--warmup", "0"])
     assert r.returncode != 0 and ("%d ranks, %d device" % (n + 1, n)) in r.stderr and not r.stdout.strip()
+
+
+def test_dump_outputs_writes_float32_and_a_seeded_sample_over_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: logits and labels as float32 .npy, whole while under the caps, else the same seeded rows every time."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    scores = torch.rand((3, 50, 19), generator=torch.Generator().manual_seed(0))
+    labels = scores.argmax(2).to(torch.uint8)
+    flat = scores.reshape(-1, 19).numpy()
+    bench.dump_outputs(str(tmp_path / "whole"), scores, labels)
+    lg, lb = np.load(str(tmp_path / "whole" / "logits.npy")), np.load(str(tmp_path / "whole" / "labels.npy"))
+    assert lg.dtype == np.float32 and lb.dtype == np.float32
+    assert np.array_equal(lg, flat) and np.array_equal(lb, labels.reshape(-1).numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LOGIT_ROWS", 40)
+    monkeypatch.setattr(bench, "DUMP_LABEL_MAX", 60)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), scores, labels)
+    got = {d: (np.load(str(tmp_path / d / "logits.npy")), np.load(str(tmp_path / d / "labels.npy"))) for d in ("a", "b")}
+    assert got["a"][0].shape == (40, 19) and got["a"][1].shape == (60,)
+    assert np.array_equal(got["a"][0], got["b"][0]) and np.array_equal(got["a"][1], got["b"][1])
+    assert np.array_equal(got["a"][0], flat[bench._seeded_rows(150, 40, 0)])
+    assert np.array_equal(got["a"][1], flat.argmax(1)[bench._seeded_rows(150, 60, 1)].astype(np.float32))
+
+
+def test_dump_outputs_is_refused_where_there_is_no_randlanet_step(tmp_path):
+    for extra in (["--stub"], ["--workload", "kpconv"], ["--train"]):
+        r = _run(extra + ["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path)])
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr and not r.stdout.strip(), extra
+    assert not os.listdir(str(tmp_path))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run: exactly --steps timed steps, ms_per_step, none of the --full measurements, and the last step's outputs on disk
+    (labels = argmax of the logits at the sampled rows)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    B, N = 8, bench.CFG["num_points"]
+    out = _line(_run(["--steps", "3", "--warmup", "1", "--frames-per-step", str(B), "--dump-outputs", str(tmp_path)]))
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert abs(out["value"] - B * 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]
+    assert out["cpu_baseline"] is None and "latency" not in out and "workloads" not in out
+    assert all(c.get("avg_launch_ms_alone") is None for c in [out["roofline"]] + out["roofline_other"])
+    lg, lb = np.load(str(tmp_path / "logits.npy")), np.load(str(tmp_path / "labels.npy"))
+    assert lg.dtype == np.float32 and lb.dtype == np.float32
+    assert lg.shape == (bench.DUMP_LOGIT_ROWS, bench.CFG["num_classes"]) and lb.shape == (B * N,)
+    assert np.isfinite(lg).all()
+    assert np.array_equal(lb[bench._seeded_rows(B * N, bench.DUMP_LOGIT_ROWS, 0)], lg.argmax(1).astype(np.float32))
