@@ -47,7 +47,7 @@ extern "C" {
 
 /* Bumped whenever a signature or a struct of this header changes (2: ml3d_radius_fill takes a spill buffer).  The Python binding   */
 /* refuses a library whose version differs from the header it was written against: a stale .so would misread its arguments.        */
-#define ML3D_ABI_VERSION 12
+#define ML3D_ABI_VERSION 13
 int ml3d_abi_version(void);
 
 /* ------------------------------------------------------------------------- */
@@ -916,6 +916,71 @@ int ml3d_randla_attention_stage_backward(const float* f, const float* enc, const
                                          int64_t n, int k, int c1, int c2, float* grad_f,
                                          float* grad_enc, float* grad_weight, float* grad_bias,
                                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* PointTransformer inference (ABI 13) -- an extension beyond SURVEY.md's scope */
+/*   table: the reference's fourth segmentation family,                         */
+/*   ml3d/torch/models/point_transformer.py.  Kernel launches only (no memset   */
+/*   nodes): every entry below can be captured into a HIP graph.                */
+/* ------------------------------------------------------------------------- */
+/* ml3d_furthest_point_sampling replaces furthest_point_sample_v2(point, row_splits, new_row_splits)                        */
+/*   (point_transformer.py:518 -> ml3d/torch/utils/pointnet/pointnet2_utils.py:66-106, the wheel's                            */
+/*   open3d.ml.torch.ops.furthest_point_sampling per batch item).  points [n_points, 3] f32; row_splits / new_row_splits      */
+/*   int64[batch + 1] on the DEVICE and the same values once more on the HOST (`_host`: the sizes are host knowledge in the   */
+/*   model, point_transformer.py:509-514, and the arguments are validated before the first HIP call);                        */
+/*   out_index int32[new_row_splits[batch]]: GLOBAL rows of `points`.  The canonical order, per item of n points, m picks:    */
+/*     - pick 0 is the item's first point; mind[i] = +inf for every i;                                                        */
+/*     - after each pick p: dx = x_i - x_p (dy, dz likewise), d2 = (dx*dx + dy*dy) + dz*dz, every operation a separately      */
+/*       rounded float32 operation (no fma); mind[i] = min(mind[i], d2);                                                      */
+/*     - the next pick is the index of the LARGEST mind, ties to the LOWEST index (a picked point has mind 0 and may be       */
+/*       picked again once every mind is 0: an item of identical points yields its first point m times).                     */
+/*   m <= n is required (ML3D_E_INVALID); an item with m == 0 writes nothing.  One workgroup per item; items of up to 65 536  */
+/*   points keep their minima in registers and need no workspace, longer ones use ml3d_fps_workspace_bytes().                 */
+size_t ml3d_fps_workspace_bytes(int64_t n_points, int64_t batch);
+
+int ml3d_furthest_point_sampling(const float* points, const int64_t* row_splits, const int64_t* new_row_splits,
+                                 const int64_t* row_splits_host, const int64_t* new_row_splits_host,
+                                 int64_t batch, int64_t n_points, int32_t* out_index, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+
+/* ml3d_pt_attention replaces Transformer.forward (point_transformer.py:416-467) after the three Linears, optionally with    */
+/*   bn2 + ReLU of the enclosing Bottleneck (:643) as the epilogue.  qkv [n, 3c] = [linear_q | linear_k | linear_v](feat)     */
+/*   (one ml3d_linear with the three matrices side by side), points [n, 3], neighbor_idx int32 [n, nsample] (global rows,    */
+/*   the self k-NN of the level; values are clamped into [0, n)).  Per query i and neighbour j:                              */
+/*     h   = relu(p_w1 (p_j - p_i) + p_b1)                  linear_p[0..2], BatchNorm folded: p_w1 [3][3] (out, in), p_b1 [3] */
+/*     r   = p_w2t^T h + p_b2                               linear_p[3]: p_w2t [3][c] (TRANSPOSED weight), p_b2 [c]           */
+/*     u   = relu(w_scale0 * (k_j - q_i + r) + w_shift0)    linear_w[0..1]: the BatchNorm as scale / shift [c]                */
+/*     g   = relu(w_w1 u + w_b1)                            linear_w[2..4], BatchNorm folded: w_w1 [R][c] (out, in), w_b1 [R], */
+/*                                                          R = 16 (c <= 128), 32 (c <= 256) or 64 rows, those >= c/8 ZERO    */
+/*     w_j = w_w2 g + w_b2                                  linear_w[5]: w_w2 [c/8][c/8] (out, in), w_b2 [c/8]                */
+/*     out[i, ch] = sum_j (v_j[ch] + r[ch]) * softmax_j(w)[j, ch mod (c/8)]                                                   */
+/*     out = relu(out * ep_scale + ep_shift) when ep_scale / ep_shift [c] are given (both or neither).                       */
+/*   c a multiple of 16 in [16, 512], nsample 8 or 16; qkv, p_w2t, p_b2, w_scale0, w_shift0 and w_w1 16-byte aligned.         */
+/*   The c -> c/8 product runs on v_mfma_f32_16x16x4_f32 (plain float32); no [n, nsample, c] tensor is written.              */
+int ml3d_pt_attention(const float* qkv, const float* points, const int32_t* neighbor_idx, int64_t n, int c, int nsample,
+                      const float* p_w1, const float* p_b1, const float* p_w2t, const float* p_b2,
+                      const float* w_scale0, const float* w_shift0, const float* w_w1, const float* w_b1,
+                      const float* w_w2, const float* w_b2, const float* ep_scale, const float* ep_shift,
+                      float* out, void* stream);
+
+/* ml3d_pt_transition_down replaces TransitionDown.forward with stride != 1 (point_transformer.py:520-533) after the FPS,    */
+/*   split by linearity: Linear([p_j - p_i | feat_j]) = W_x (p_j - p_i) + W_f feat_j, and y = feat W_f^T [n_src, c_out] is    */
+/*   computed ONCE PER SOURCE POINT by the caller (ml3d_linear).  For sampled point i = sample_idx[i] (int32 [m], global row */
+/*   of `points`, the FPS result) with neighbours neighbor_idx int32 [m, nsample] (global rows):                              */
+/*     out[i, ch] = max_j relu(scale[ch] * (y[idx_j, ch] + sum_d w_x[d][ch] (p_j - p_i)[d]) + shift[ch])                       */
+/*   w_x [3][c_out] (the first three input columns of the Linear, transposed), scale / shift = the folded BatchNorm (the     */
+/*   maximum is taken AFTER the affine step: the scale may be negative).  out_points [m, 3] (may be NULL) receives           */
+/*   points[sample_idx].                                                                                                      */
+int ml3d_pt_transition_down(const float* y, const float* points, int64_t n_src, const int32_t* sample_idx,
+                            const int32_t* neighbor_idx, int64_t m, int nsample, int c_out, const float* w_x,
+                            const float* scale, const float* shift, float* out, float* out_points, void* stream);
+
+/* ml3d_pt_interpolate replaces interpolation() (point_transformer.py:737-776) and the add of TransitionUp.forward (:597):   */
+/*   out[i] = a[i] + sum_{t < k} w_t b[idx[i, t]],  w_t = (1 / (d2_t + 1e-8)) / sum_t (1 / (d2_t + 1e-8))                       */
+/*   with idx int32 [n, k] / dist2 f32 [n, k] exactly as ml3d_knn_search returns them (k = 3 in the model, <= 16),           */
+/*   a [n, c] (NULL: no add), b [n_src, c].                                                                                   */
+int ml3d_pt_interpolate(const float* a, const float* b, int64_t n_src, const int32_t* idx, const float* dist2,
+                        int64_t n, int k, int c, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ _lib = None
 
 ERRORS = {-1: "invalid argument", -2: "workspace too small", -3: "HIP launch failed", -4: "unsupported configuration"}
 
-ABI_VERSION = 12         # ML3D_ABI_VERSION of include/ml3d_hip.h (checked against the loaded library in get())
+ABI_VERSION = 13         # ML3D_ABI_VERSION of include/ml3d_hip.h (checked against the loaded library in get())
 
 # every symbol include/ml3d_hip.h declares (checked by tests/test_abi_symbols.py)
 SYMBOLS = [
@@ -94,6 +94,8 @@ SYMBOLS = [
     "ml3d_kpconv_deformed_weighted", "ml3d_kpconv_deformed_weighted_backward",
     "ml3d_kpconv_offset_regulariser_blocks", "ml3d_kpconv_offset_regulariser",
     "ml3d_randla_attention_stage", "ml3d_randla_attention_stage_backward_workspace_bytes", "ml3d_randla_attention_stage_backward",
+    "ml3d_fps_workspace_bytes", "ml3d_furthest_point_sampling", "ml3d_pt_attention", "ml3d_pt_transition_down",
+    "ml3d_pt_interpolate",
 ]
 
 
@@ -280,6 +282,16 @@ def bind(lib):
     lib.ml3d_randla_attention_stage_backward_workspace_bytes.restype = sz
     lib.ml3d_randla_attention_stage_backward_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.ml3d_randla_attention_stage_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.ml3d_fps_workspace_bytes.restype = sz
+    lib.ml3d_fps_workspace_bytes.argtypes = [i64, i64]
+    lib.ml3d_furthest_point_sampling.restype = C.c_int
+    lib.ml3d_furthest_point_sampling.argtypes = [vp, vp, vp, vp, vp, i64, i64, vp, vp, sz, vp]
+    lib.ml3d_pt_attention.restype = C.c_int
+    lib.ml3d_pt_attention.argtypes = [vp, vp, vp, i64, i32, i32] + [vp] * 12 + [vp, vp]
+    lib.ml3d_pt_transition_down.restype = C.c_int
+    lib.ml3d_pt_transition_down.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.ml3d_pt_interpolate.restype = C.c_int
+    lib.ml3d_pt_interpolate.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, vp, vp]
     lib.ml3d_vote_update.restype = C.c_int
     lib.ml3d_vote_update.argtypes = [vp, vp, i64, i32, f32, vp, i64, vp]
     lib.ml3d_argmax_labels.restype = C.c_int

@@ -20,3 +20,4 @@ from .detection import (pillar_features, conv2d_nhwc, pack_bf16x3, linear_bf16x3
 from .sampler import nearest_to_center, argmax_labels, vote_update, device_patch   # noqa: F401
 from .train import (gemm_tn, LinearFunction, BatchNormActFunction, batch_norm_act, GatherRowsFunction, GatherPoolFunction,   # noqa: F401
                     AttentionStageFunction, attention_stage_supported, KPConvDeformedFunction, OffsetRegulariserFunction)
+from .pointtransformer import furthest_point_sampling, pt_attention, pt_transition_down, pt_interpolate   # noqa: F401

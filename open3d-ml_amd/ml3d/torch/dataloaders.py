@@ -102,6 +102,38 @@ class ObjectDetectBatch:
         return self
 
 
+class PointTransformerBatch:
+    """concat_batcher.py:455-485: the clouds of a batch concatenated, delimited by ``row_splits`` (kept on the host as
+    ``row_splits_host`` too: every level size of the forward follows from it without a device read-back)."""
+
+    def __init__(self, batches):
+        pc, feat, label, splits = [], [], [], [0]
+        for batch in batches:
+            data = batch['data']
+            pc.append(torch.as_tensor(data['point'], dtype=torch.float32))
+            if data.get('feat') is not None:
+                feat.append(torch.as_tensor(data['feat'], dtype=torch.float32))
+            label.append(torch.as_tensor(data['label'], dtype=torch.int64))
+            splits.append(splits[-1] + int(pc[-1].shape[0]))
+        self.point = torch.cat(pc, 0)
+        self.feat = torch.cat(feat, 0) if feat else None
+        self.label = torch.cat(label, 0)
+        self.row_splits = torch.tensor(splits, dtype=torch.int64)
+        self.row_splits_host = np.asarray(splits, dtype=np.int64)
+
+    def pin_memory(self):
+        self.point = self.point.pin_memory()
+        self.feat = None if self.feat is None else self.feat.pin_memory()
+        self.label = self.label.pin_memory()
+        return self
+
+    def to(self, device):
+        self.point = self.point.to(device, non_blocking=True)
+        self.feat = None if self.feat is None else self.feat.to(device, non_blocking=True)
+        self.label = self.label.to(device, non_blocking=True)
+        return self
+
+
 class ConcatBatcher(object):
 
     def __init__(self, device, model='KPConv'):
@@ -113,7 +145,10 @@ class ConcatBatcher(object):
             return {'data': self._kpconv(batches), 'attr': []}
         if self.model in ("PointPillars", "PointRCNN"):
             return ObjectDetectBatch(batches)
-        raise Exception("ConcatBatcher (MI355X build): model '%s' is outside the hot path (KPFCNN, PointPillars)" % self.model)
+        if self.model == "PointTransformer":
+            return {'data': PointTransformerBatch(batches), 'attr': []}
+        raise Exception("ConcatBatcher (MI355X build): model '%s' is outside the hot path (KPFCNN, PointPillars, "
+                        "PointTransformer)" % self.model)
 
     def _kpconv(self, batches):
         from .models.kpconv import KPConvBatch

@@ -1,4 +1,5 @@
-"""``open3d.ml.torch.ops`` — the five ops the inference hot path takes from the wheel.
+"""``open3d.ml.torch.ops`` — the five ops the inference hot path takes from the wheel and
+``furthest_point_sampling`` for the PointTransformer extension.
 
 Each function accepts the tensors the reference passes — CPU tensors from collate code (``kpconv.py:2021-2032``), GPU
 tensors from the models, small CPU tensors for voxel sizes (``point_pillars.py:317-320``) — runs on the MI355X and
@@ -60,17 +61,31 @@ def nms(boxes, scores, nms_overlap_thresh):
     return _P.back(_P.ops().nms(b, s, float(nms_overlap_thresh)), src)
 
 
+def furthest_point_sampling(points, sample_size):
+    """points [B, N, 3] -> int32 [B, sample_size], item-local indices (``ml3d/torch/utils/pointnet/pointnet2_utils.py:94``;
+    ``sample_size`` may be a 0-d tensor) in the canonical order of ``ml3d_furthest_point_sampling``: first point first,
+    float32 distances, ties to the lowest index."""
+    p, src = _P.to_dev(points, torch.float32)
+    if p.dim() != 3 or p.shape[2] != 3:
+        raise ValueError("furthest_point_sampling: points must be [B, N, 3]")
+    B, N, m = int(p.shape[0]), int(p.shape[1]), int(sample_size)
+    rs, nrs = [b * N for b in range(B + 1)], [b * m for b in range(B + 1)]
+    idx = _P.ops().furthest_point_sampling(p.reshape(B * N, 3).contiguous(), rs, nrs).reshape(B, m)
+    base = torch.arange(B, dtype=torch.int32, device=idx.device)[:, None] * N
+    return _P.back(idx - base, src)
+
+
 def _out_of_scope(name):
     def fn(*args, **kwargs):
         raise NotImplementedError("open3d.ml.torch.ops.%s belongs to a model outside this repository's scope (SURVEY.md §2: "
-                                  "PointRCNN / SparseConvNet / PVCNN / PointTransformer); only its import target exists" % name)
+                                  "PointRCNN / SparseConvNet / PVCNN); only its import target exists" % name)
     fn.__name__ = name
     return fn
 
 
 # import targets of the reference's out-of-scope models (ml3d/torch/models/{sparseconvnet,pvcnn,point_rcnn}.py,
 # ml3d/torch/utils/{pointnet,roipool3d}): resolvable so that `import ml3d.torch.models` works, inert otherwise
-for _n in ("reduce_subarrays_sum", "roi_pool", "furthest_point_sampling", "three_nn", "three_interpolate",
+for _n in ("reduce_subarrays_sum", "roi_pool", "three_nn", "three_interpolate",
            "three_interpolate_grad", "ball_query", "trilinear_devoxelize_forward", "trilinear_devoxelize_backward",
            "continuous_conv", "sparse_conv", "sparse_conv_transpose", "invert_neighbors_list", "build_spatial_hash_table"):
     globals()[_n] = _out_of_scope(_n)
