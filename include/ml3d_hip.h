@@ -982,6 +982,64 @@ int ml3d_pt_transition_down(const float* y, const float* points, int64_t n_src, 
 int ml3d_pt_interpolate(const float* a, const float* b, int64_t n_src, const int32_t* idx, const float* dist2,
                         int64_t n, int k, int c, float* out, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* PVCNN inference (added at ABI 13: new symbols only, no signature changed) -- */
+/*   the reference's ml3d/torch/models/pvcnn.py.  Kernel launches only.         */
+/* ------------------------------------------------------------------------- */
+/* ml3d_pvcnn_voxel_coords replaces the normalisation of Voxelization.forward (pvcnn.py:653-662) with an EXACT contract: a   */
+/*   coordinate 1 ulp across a rounding boundary moves a point to another voxel, so the arithmetic is fixed operation by      */
+/*   operation.  coords [batch, 3, n] f32 (the reference's layout).  Per item:                                                */
+/*     1. mean_c = float32(sum_n double(x_c[n])) / float32(n)       (double sum in a fixed order, rounded once, f32 division)  */
+/*     2. d = x - mean                                             (float32)                                                  */
+/*     3. norm_n = sqrt(fma(dz, dz, fma(dy, dy, dx * dx)))         (float32, correctly rounded)                               */
+/*     4. scale = max_n norm_n * 2.0f + 1e-6f                                                                                 */
+/*     5. per resolution r: v = min(max((d / scale + 0.5f) * float(r), 0), r - 1), a true division; cell = (int) rintf(v)     */
+/*        (half to even); flat index = (cell_x * r + cell_y) * r + cell_z.                                                    */
+/*   stats [batch, 4] = (mean x, y, z, scale).  resolutions_host int32[num_resolutions] (<= 8 of them, each in [1, 1024]);    */
+/*   out_v_host / out_index_host: HOST arrays of num_resolutions DEVICE pointers, v f32 [batch * n, 3] and the flat index     */
+/*   int32 [batch * n].  Steps 1-4 do not depend on r: one call serves every resolution of a forward.                         */
+int ml3d_pvcnn_voxel_coords(const float* coords, int64_t batch, int64_t n, const int32_t* resolutions_host,
+                            int num_resolutions, float* stats, float* const* out_v_host,
+                            int32_t* const* out_index_host, void* stream);
+
+/* ml3d_avg_voxelize replaces avg_voxelize (pvcnn.py:579-619) on a CHANNELS-LAST grid [batch, r^3, ldg] (16-byte aligned):    */
+/*   grid[b, cell, ch] = (sum over the item's points with vox_index == cell of feat[row, ch]) / max(count, 1), ch < c;        */
+/*   columns c .. ldg - 1 and cells without a point are zero.  feat rows [batch * n] of stride ldf.  The sum runs in          */
+/*   ASCENDING point order (a stable sort by cell, then one serial sum per cell): deterministic, the order of a serial        */
+/*   scatter_add; no float atomics.  vox_index outside [0, r^3) drops the point.  r <= 64.                                    */
+size_t ml3d_avg_voxelize_workspace_bytes(int64_t batch, int64_t n);
+
+int ml3d_avg_voxelize(const float* feat, int64_t ldf, int c, const int32_t* vox_index, int64_t batch, int64_t n, int r,
+                      float* grid, int64_t ldg, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ml3d_conv3d_ndhwc_bf16x3 replaces Conv3d(3, stride 1, padding 1) + BatchNorm3d + LeakyReLU of PVConv.voxel_layers          */
+/*   (pvcnn.py:538-553) on a channels-last volume in [batch, d, h, w, cin] -> out [batch, d, h, w] voxels of stride           */
+/*   out_voxel_stride.  packed = ml3d_gemm_pack_bf16x3 of the weights [((kd * 3 + kh) * 3 + kw) * cin + ci, cout] (the         */
+/*   reference's [cout, cin, 3, 3, 3] permuted, the BatchNorm folded in); bias [cout] or NULL; act / slope as ml3d_linear.    */
+/*   Implicit GEMM on the bf16 matrix pipe with three-way splits (float32-equivalent: ml3d_gemm_pack_bf16x3); the zero        */
+/*   padding is never read.  cin % 32 == 0 (pad narrower inputs with zero channels and zero weight rows), `in` 16-byte        */
+/*   aligned, fewer than 2^31 input elements; ML3D_E_UNSUPPORTED otherwise.                                                   */
+int ml3d_conv3d_ndhwc_bf16x3(const float* in, int64_t batch, int d, int h, int w, int cin, const void* packed,
+                             const float* bias, int act, float slope, int cout, float* out, int64_t out_voxel_stride,
+                             void* stream);
+
+/* ml3d_trilinear_devoxelize replaces trilinear_devoxelize_forward (pvcnn.py:37, inference: no inds / wgts) and the add of    */
+/*   PVConv.forward (:575).  grid [batch, r^3, ldg] channels-last, v [batch * n, 3] as ml3d_pvcnn_voxel_coords wrote it.      */
+/*   Per axis lo = floor(v), f = v - lo, hi = lo + (f > 0 ? 1 : 0) (both clamped into [0, r - 1]);                            */
+/*     out[row, ch] = sum over the 8 corners (x, y, z in {lo, hi}, z fastest) of (wx * wy) * wz * grid[b, corner, ch]          */
+/*                    (+ addend[row, ch]),   w = 1 - f at lo, f at hi.                                                        */
+/*   out rows of stride ldc, addend (may be NULL, may alias out) rows of stride lda: a PVConv's fused feature lands in its     */
+/*   column slice of a wider buffer.                                                                                          */
+int ml3d_trilinear_devoxelize(const float* grid, int64_t ldg, int r, int c, const float* v, int64_t batch, int64_t n,
+                              const float* addend, int64_t lda, float* out, int64_t ldc, void* stream);
+
+/* ml3d_segment_max_rows replaces feat.max(dim=-1) (pvcnn.py:156) on rows: x [batch * n] rows of stride ldx, c columns ->     */
+/*   out[b, ch] = max over the item's n rows.  Two steps through the workspace, no atomics.                                  */
+size_t ml3d_segment_max_rows_workspace_bytes(int64_t batch, int64_t n, int c);
+
+int ml3d_segment_max_rows(const float* x, int64_t ldx, int64_t batch, int64_t n, int c, float* out, int64_t ldo,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

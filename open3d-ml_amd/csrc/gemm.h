@@ -62,6 +62,13 @@ struct ConvA {
     int KH, KW, stride, pad;
 };
 
+// implicit im2col of a channels-last volume for the 3 x 3 x 3 / stride 1 / pad 1 convolution: m = (b, z, y, x),
+// k = ((kd * 3 + kh) * 3 + kw) * C + ci
+struct Conv3dA {
+    const float* in;     // [B, D, H, W, C]
+    int B, D, H, W, C;
+};
+
 size_t gemm_partial_bytes(int64_t M, int N, int K);   // workspace for the split-K partials (may be 0)
 
 int gemm_rows(const RowsA& A, const float* Bm, int64_t M, int N, int K, const Epilogue& ep, float* C, int64_t ldc,
@@ -82,5 +89,10 @@ size_t gemm_partial_bytes_bf16x3(int64_t M, int N, int K);
 int gemm_rows_bf16x3(const float* a, int64_t lda, int k1, const float* a2, int64_t lda2, int k2, int64_t M, const void* packed,
                      int N, const Epilogue& ep, float* C, int64_t ldc, void* partial_ws, size_t partial_bytes, hipStream_t stream);
 int gemm_conv_bf16x3(const ConvA& A, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc, hipStream_t stream);
+
+// 3 x 3 x 3 / stride 1 / pad 1 convolution of a channels-last volume on the same kernel (C % 32 == 0, 32-bit offsets:
+// gemm_conv3d_bf16x3_ok); packed = gemm_pack_bf16x3 of the [27 C, N] weights
+bool gemm_conv3d_bf16x3_ok(const Conv3dA& A);
+int gemm_conv3d_bf16x3(const Conv3dA& A, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc, hipStream_t stream);
 
 }  // namespace ml3d

@@ -555,6 +555,58 @@ struct RowsLoader2 {
     }
 };
 
+// implicit im2col of a channels-last VOLUME [B, D, H, W, C] for the 3 x 3 x 3 / stride 1 / pad 1 convolution (PVCNN's voxel branch):
+// ConvLoader2 with one more axis.  Row m = (b, z, y, x); k = ((kd * 3 + kh) * 3 + kw) * C + ci.  The 27 taps fit the 32-bit mask; a
+// 32-deep chunk lies inside one tap (C % 32 == 0); the walk carries (tap, element offset of the tap) on the scalar unit: + C per tap
+// (the voxel to the right is contiguous), + (W - 3) C at the end of a kw run, + (H - 3) W C at the end of a kh run.  A tap the zero
+// padding removes is never dereferenced (its float4 is zero), so `off` may point in front of the volume.
+struct Conv3dLoader {
+    Conv3dA A;
+    int64_t M;
+    int K;
+    struct Ctx { int off; unsigned taps; };
+    __device__ __forceinline__ Ctx prepare(int64_t m) const {
+        Ctx c; c.off = 0; c.taps = 0u;
+        if (m < M) {
+            const unsigned mu = (unsigned)m;                 // (M = B D H W < 2^31: checked on the host)
+            const unsigned t1 = mu / (unsigned)A.W;
+            const int x = (int)(mu - t1 * (unsigned)A.W);
+            const unsigned t2 = t1 / (unsigned)A.H;
+            const int y = (int)(t1 - t2 * (unsigned)A.H);
+            const int b = (int)(t2 / (unsigned)A.D);
+            const int z = (int)(t2 - (unsigned)b * (unsigned)A.D);
+            c.off = (((b * A.D + z - 1) * A.H + y - 1) * A.W + x - 1) * A.C;
+            for (int kd = 0; kd < 3; ++kd)
+                for (int kh = 0; kh < 3; ++kh)
+                    for (int kw = 0; kw < 3; ++kw)
+                        if (z + kd >= 1 && z + kd <= A.D && y + kh >= 1 && y + kh <= A.H && x + kw >= 1 && x + kw <= A.W)
+                            c.taps |= 1u << ((kd * 3 + kh) * 3 + kw);
+        }
+        return c;
+    }
+    struct Walk { int tap, kw, kh, ci, toff; };
+    __device__ __forceinline__ Walk walk_begin(int /* k0 == 0: never split along K */) const {
+        Walk w; w.tap = 0; w.kw = 0; w.kh = 0; w.ci = 0; w.toff = 0; return w;
+    }
+    __device__ __forceinline__ void walk_next(Walk& w, int kc) const {
+        w.ci += kc;
+        w.toff += kc;
+        if (w.ci >= A.C) {
+            w.ci = 0;
+            ++w.tap;
+            if (++w.kw == 3) {
+                w.kw = 0;
+                w.toff += (A.W - 3) * A.C;
+                if (++w.kh == 3) { w.kh = 0; w.toff += (A.H - 3) * A.W * A.C; }
+            }
+        }
+    }
+    __device__ __forceinline__ float4 load4w(const Ctx& c, const Walk& w, int kq) const {
+        if (!((c.taps >> w.tap) & 1u)) return make_float4(0.f, 0.f, 0.f, 0.f);
+        return *reinterpret_cast<const float4*>(A.in + (c.off + w.toff + kq));
+    }
+};
+
 // XCD-aware tile order.  Workgroups are dealt to the 8 XCDs round-robin by their linear id, and every XCD has its own L2: with
 // the identity mapping the 128-row tiles that share input rows (the 3 x 3 taps of neighbouring pixels) sit on 8 different L2s
 // and each XCD streams nearly the whole image.  Here XCD x owns a CONTIGUOUS run of tiles (the column tiles of one row tile
@@ -1324,6 +1376,25 @@ int gemm_conv_bf16x3(const ConvA& A, const void* packed, int N, const Epilogue& 
     }
     if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<ConvLoader2, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L2, (const u32x4*)packed, N, Npad, ep, C, ldc, L2.K, (float*)nullptr);
     else hipLaunchKernelGGL((gemm_tile_bf3<ConvLoader2, 64>), dim3(gm, 1u), dim3(256), 0, st, L2, (const u32x4*)packed, N, Npad, ep, C, ldc, L2.K, (float*)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+// 3 x 3 x 3 / stride 1 / pad 1 on a channels-last volume (gemm.h): the general bf16x3 tile kernel behind Conv3dLoader
+bool gemm_conv3d_bf16x3_ok(const Conv3dA& A) {
+    if (!A.in || A.B <= 0 || A.D <= 0 || A.H <= 0 || A.W <= 0 || A.C <= 0 || (A.C % BF_KC) != 0 || (((uintptr_t)A.in) & 15) != 0) return false;
+    const int64_t M = (int64_t)A.B * A.D * A.H * A.W;
+    // 32-bit element offsets, the corner one voxel outside on every axis included
+    return M < 0x7fffffffll && M * A.C < 0x7fffffffll - ((int64_t)A.H * A.W + A.W + 1) * A.C;
+}
+
+int gemm_conv3d_bf16x3(const Conv3dA& A, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc, hipStream_t st) {
+    if (!gemm_conv3d_bf16x3_ok(A) || !packed || !C || N <= 0 || ep.res_gather || ep.ps) return ML3D_E_INVALID;
+    Conv3dLoader L;
+    L.A = A; L.M = (int64_t)A.B * A.D * A.H * A.W; L.K = 27 * A.C;
+    const int Npad = bf3_npad(N);
+    const unsigned gm = (unsigned)((L.M + G2_BM - 1) / G2_BM);
+    if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<Conv3dLoader, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
+    else hipLaunchKernelGGL((gemm_tile_bf3<Conv3dLoader, 64>), dim3(gm, 1u), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 

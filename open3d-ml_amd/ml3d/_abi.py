@@ -96,6 +96,8 @@ SYMBOLS = [
     "ml3d_randla_attention_stage", "ml3d_randla_attention_stage_backward_workspace_bytes", "ml3d_randla_attention_stage_backward",
     "ml3d_fps_workspace_bytes", "ml3d_furthest_point_sampling", "ml3d_pt_attention", "ml3d_pt_transition_down",
     "ml3d_pt_interpolate",
+    "ml3d_pvcnn_voxel_coords", "ml3d_avg_voxelize_workspace_bytes", "ml3d_avg_voxelize", "ml3d_conv3d_ndhwc_bf16x3",
+    "ml3d_trilinear_devoxelize", "ml3d_segment_max_rows_workspace_bytes", "ml3d_segment_max_rows",
 ]
 
 
@@ -292,6 +294,20 @@ def bind(lib):
     lib.ml3d_pt_transition_down.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.ml3d_pt_interpolate.restype = C.c_int
     lib.ml3d_pt_interpolate.argtypes = [vp, vp, i64, vp, vp, i64, i32, i32, vp, vp]
+    lib.ml3d_pvcnn_voxel_coords.restype = C.c_int
+    lib.ml3d_pvcnn_voxel_coords.argtypes = [vp, i64, i64, vp, i32, vp, vp, vp, vp]
+    lib.ml3d_avg_voxelize_workspace_bytes.restype = sz
+    lib.ml3d_avg_voxelize_workspace_bytes.argtypes = [i64, i64]
+    lib.ml3d_avg_voxelize.restype = C.c_int
+    lib.ml3d_avg_voxelize.argtypes = [vp, i64, i32, vp, i64, i64, i32, vp, i64, vp, sz, vp]
+    lib.ml3d_conv3d_ndhwc_bf16x3.restype = C.c_int
+    lib.ml3d_conv3d_ndhwc_bf16x3.argtypes = [vp, i64, i32, i32, i32, i32, vp, vp, i32, f32, i32, vp, i64, vp]
+    lib.ml3d_trilinear_devoxelize.restype = C.c_int
+    lib.ml3d_trilinear_devoxelize.argtypes = [vp, i64, i32, i32, vp, i64, i64, vp, i64, vp, i64, vp]
+    lib.ml3d_segment_max_rows_workspace_bytes.restype = sz
+    lib.ml3d_segment_max_rows_workspace_bytes.argtypes = [i64, i64, i32]
+    lib.ml3d_segment_max_rows.restype = C.c_int
+    lib.ml3d_segment_max_rows.argtypes = [vp, i64, i64, i64, i32, vp, i64, vp, sz, vp]
     lib.ml3d_vote_update.restype = C.c_int
     lib.ml3d_vote_update.argtypes = [vp, vp, i64, i32, f32, vp, i64, vp]
     lib.ml3d_argmax_labels.restype = C.c_int

@@ -21,3 +21,5 @@ from .sampler import nearest_to_center, argmax_labels, vote_update, device_patch
 from .train import (gemm_tn, LinearFunction, BatchNormActFunction, batch_norm_act, GatherRowsFunction, GatherPoolFunction,   # noqa: F401
                     AttentionStageFunction, attention_stage_supported, KPConvDeformedFunction, OffsetRegulariserFunction)
 from .pointtransformer import furthest_point_sampling, pt_attention, pt_transition_down, pt_interpolate   # noqa: F401
+from .pvcnn import (pvcnn_voxel_coords, avg_voxelize, pack_conv3d_weights, conv3d_ndhwc, trilinear_devoxelize,   # noqa: F401
+                    segment_max_rows, linear_rows_bf16x3)
