@@ -1040,6 +1040,65 @@ size_t ml3d_segment_max_rows_workspace_bytes(int64_t batch, int64_t n, int c);
 int ml3d_segment_max_rows(const float* x, int64_t ldx, int64_t batch, int64_t n, int c, float* out, int64_t ldo,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* SparseConvUnet inference (added at ABI 13: new symbols only, no signature  */
+/*   changed) -- the reference's ml3d/torch/models/sparseconvnet.py.          */
+/*   Kernel launches only; nothing is read back.                              */
+/* ------------------------------------------------------------------------- */
+/* CONTRACT (UNPINNED against the open3d wheel: SparseConv / SparseConvTranspose / voxelize live in the wheel, which is not   */
+/* available to this project; the semantics below are derived from the reference's call sites and load_unet_wts):             */
+/*   positions   voxel centres int + 0.5 with integer coordinates in [0, grid_size), grid_size <= 4096; the batch item is     */
+/*               part of a voxel's identity (two items never see each other's voxels).                                        */
+/*   row order   at every level rows ascend in (item, x, y, z) -- per item what torch.unique(dim=0) of calculate_grid gives.  */
+/*               (Level 0 of the reference has voxelize's order; immaterial: outputs return to points through index_map.)     */
+/*   level l+1   the distinct coord >> 1 of level l  (= calculate_grid followed by / 2).                                      */
+/*   submanifold 3x3x3   out[o] = sum_t W[t] in[row(o + d)],  d in {-1,0,1}^3,  t = (dz+1)*9 + (dy+1)*3 + (dx+1); the kernel     */
+/*               parameter is [kz, ky, kx, Cin, Cout] (x fastest among the taps: load_unet_wts' (2,1,0,3,4) transpose);       */
+/*               absent neighbours contribute nothing; no bias.                                                               */
+/*   strided 2x2x2 (Convolution, offset -0.5)   out[p] = sum over existing children c of p of W[t] in[c],                      */
+/*               t = pz*4 + py*2 + px with p* the child's coordinate parities.                                                */
+/*   transposed 2x2x2 (DeConvolution)   out[c] = W[t] in[parent(c)], same t; kernel parameter [2,2,2,Cin,Cout].                */
+/*   InputLayer  per-voxel mean of the feature columns over the voxel's points, summed in ASCENDING point order (float32,     */
+/*               deterministic, no float atomics), divided once; index_map[point] = row.                                      */
+/*   BatchNormBlock   eval-mode running statistics, eps = 1e-4.                                                               */
+/*                                                                                                                            */
+/* ml3d_scn_build builds EVERY level in one call.  points f32 [n, 3] (all items concatenated), feat rows [n] of stride ldf    */
+/*   with feat_channels <= 4 columns, row_splits_host int64 [batch + 1] (HOST), batch <= 4096, levels <= 12.  Keys are        */
+/*   (item << 36) | (x << 24) | (y << 12) | z, sorted with the stable 64-bit radix sort; neighbours by binary search in the   */
+/*   sorted unique keys; a coordinate outside [0, grid_size) never forms a key.  Outputs, every per-level array at a fixed    */
+/*   stride of n rows (M_l <= n), level l at element offset l * n * width:                                                    */
+/*     counts  int32 [levels]            M_l  (DEVICE memory: a forward reads this vector back once)                          */
+/*     coords  int32 [levels, n, 4]      (item, x, y, z) of a row                                                             */
+/*     nbr27   int32 [levels, n, 27]     row of the neighbour at tap t, -1 if absent (t = 13 is the row itself)               */
+/*     child8  int32 [levels, n, 8]      level l >= 1: the level l - 1 row of child t of a row, -1 if absent (level 0 unused) */
+/*     parent  int32 [levels, n], ptap int32 [levels, n]     level l < levels - 1: row at level l + 1, parity tap             */
+/*     up8     int32 [levels, n, 8]      the transposed rulebook: parent at column ptap, -1 elsewhere                         */
+/*     index_map int32 [n]               level-0 row of a point (-1: the point lies outside the grid)                         */
+/*     feat0   f32 rows [M_0] of stride ldo: the mean features (columns >= feat_channels are not written)                     */
+size_t ml3d_scn_build_workspace_bytes(int64_t n, int levels);
+
+int ml3d_scn_build(const float* points, const float* feat, int64_t ldf, int feat_channels, int64_t n,
+                   const int64_t* row_splits_host, int batch, int levels, int grid_size, int32_t* counts, int32_t* coords,
+                   int32_t* nbr27, int32_t* child8, int32_t* parent, int32_t* ptap, int32_t* up8, int32_t* index_map,
+                   float* feat0, int64_t ldo, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ml3d_sparse_conv_bf16x3: out[r, :n] = act( sum_{t < taps} in[rule[r, t], :cp] W[t*cp : (t+1)*cp] + a2[r, :k2] W[taps*cp :]    */
+/*                                           + bias + residual[r] ),  r < m.                                                  */
+/*   in rows [in_rows] of stride ldi, cp = the PADDED channel count (cp % 32 == 0; pad narrower inputs with zero columns and   */
+/*   zero weight rows); rule int32 [m, taps] (taps = 27, 8, or 1 for a gathered Linear), an entry outside [0, in_rows)          */
+/*   contributes nothing and is never dereferenced; a2 (NULL with k2 = 0) an optional dense block of k2 % 32 == 0 columns;     */
+/*   packed = ml3d_gemm_pack_bf16x3 of the [taps * cp + k2, n] weights; bias [n] / residual rows of stride ldr may be NULL;    */
+/*   act / slope as ml3d_linear.  Implicit GEMM on the bf16 matrix pipe with three-way splits (float32-equivalent), no         */
+/*   atomics: the same input gives the same bits.  in / a2 16-byte aligned, ldi / lda2 % 4 == 0; ML3D_E_UNSUPPORTED otherwise. */
+int ml3d_sparse_conv_bf16x3(const float* in, int64_t ldi, int64_t in_rows, int cp, const int32_t* rule, int taps, int64_t m,
+                            const float* a2, int64_t lda2, int k2, const void* packed, int n, const float* bias,
+                            const float* residual, int64_t ldr, int act, float slope, float* out, int64_t ldc, void* stream);
+
+/* ml3d_scn_bn_relu: out[r, ch] = max(in[r, ch] * scale[ch] + shift[ch], 0) on m rows of c columns (row strides ldi / ldo):   */
+/*   BatchNormBlock + ReLUBlock in front of a convolution whose input is also used raw.                                       */
+int ml3d_scn_bn_relu(const float* in, int64_t ldi, int64_t m, int c, const float* scale, const float* shift, float* out,
+                     int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

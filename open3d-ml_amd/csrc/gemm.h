@@ -69,6 +69,16 @@ struct Conv3dA {
     int B, D, H, W, C;
 };
 
+// rulebook gather of a sparse voxel set (SparseConvUnet): row m reads, for tap t < taps, input row rule[m * taps + t] (< 0 or
+// >= in_rows: the tap contributes nothing and is never dereferenced); k = t * cp + ci with cp the padded channel count
+// (cp % 32 == 0, cp <= ldi).  An optional dense block a2 [M, k2] follows as columns taps * cp .. (a ResidualBlock's
+// NetworkInNetwork Linear riding in the same GEMM)
+struct SparseConvA {
+    const float* in; int64_t ldi; int64_t in_rows; int cp;
+    const int32_t* rule; int taps;
+    const float* a2; int64_t lda2; int k2;
+};
+
 size_t gemm_partial_bytes(int64_t M, int N, int K);   // workspace for the split-K partials (may be 0)
 
 int gemm_rows(const RowsA& A, const float* Bm, int64_t M, int N, int K, const Epilogue& ep, float* C, int64_t ldc,
@@ -94,5 +104,10 @@ int gemm_conv_bf16x3(const ConvA& A, const void* packed, int N, const Epilogue& 
 // gemm_conv3d_bf16x3_ok); packed = gemm_pack_bf16x3 of the [27 C, N] weights
 bool gemm_conv3d_bf16x3_ok(const Conv3dA& A);
 int gemm_conv3d_bf16x3(const Conv3dA& A, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc, hipStream_t stream);
+
+// sparse convolution by rulebook on the same kernel (SparseConvLoader): packed = gemm_pack_bf16x3 of the [taps * cp + k2, N]
+// weights.  ML3D_E_UNSUPPORTED unless cp % 32 == 0, k2 % 32 == 0, ldi / lda2 % 4 == 0 and in / a2 are 16-byte aligned
+int gemm_sparse_conv_bf16x3(const SparseConvA& A, int64_t M, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc,
+                            hipStream_t stream);
 
 }  // namespace ml3d

@@ -607,6 +607,47 @@ struct Conv3dLoader {
     }
 };
 
+// rulebook gather of a sparse voxel set (SparseConvUnet's submanifold 3 x 3 x 3, strided 2 x 2 x 2 and transposed convolutions and
+// the final Linear gathered through index_map): row m, tap t reads input row rule[m * taps + t]; k = t * cp + ci, so a 32-deep
+// chunk lies inside one tap (cp % 32 == 0) and the walk carries (tap, channel origin) on the scalar unit.  Conv3dLoader's mask in a
+// register does not apply -- the rule row IS the mask: a staged row reads its ONE rule entry of the chunk (4 bytes beside the 16 of
+// the float4 it fetches; the 8 lanes that stage a row's 32 channels read the same word, one request), and an entry outside
+// [0, in_rows) -- the -1 of an absent neighbour -- gives a zero float4 without a dereference.  Past the taps an optional dense
+// block a2 [M, k2] supplies further columns (RowsLoader2's second block).
+struct SparseConvLoader {
+    SparseConvA A;
+    int64_t M;
+    int K;
+    struct Ctx { const int32_t* r; const float* p2; };
+    __device__ __forceinline__ Ctx prepare(int64_t m) const {
+        Ctx c;
+        c.r = m < M ? A.rule + m * A.taps : nullptr;
+        c.p2 = (m < M && A.a2) ? A.a2 + m * A.lda2 : nullptr;
+        return c;
+    }
+    struct Walk { int tap, ci; };
+    __device__ __forceinline__ Walk walk_begin(int k0) const {
+        Walk w;
+        w.tap = k0 / A.cp;
+        if (w.tap > A.taps) w.tap = A.taps;
+        w.ci = k0 - w.tap * A.cp;
+        return w;
+    }
+    __device__ __forceinline__ void walk_next(Walk& w, int kc) const {
+        w.ci += kc;
+        if (w.tap < A.taps && w.ci >= A.cp) { w.ci = 0; ++w.tap; }
+    }
+    __device__ __forceinline__ float4 load4w(const Ctx& c, const Walk& w, int kq) const {
+        if (w.tap < A.taps) {                                        // (uniform)
+            if (!c.r) return make_float4(0.f, 0.f, 0.f, 0.f);
+            const int e = c.r[w.tap];
+            if ((unsigned)e >= (unsigned)A.in_rows) return make_float4(0.f, 0.f, 0.f, 0.f);
+            return *reinterpret_cast<const float4*>(A.in + (int64_t)e * A.ldi + w.ci + kq);
+        }
+        return c.p2 ? *reinterpret_cast<const float4*>(c.p2 + w.ci + kq) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+};
+
 // XCD-aware tile order.  Workgroups are dealt to the 8 XCDs round-robin by their linear id, and every XCD has its own L2: with
 // the identity mapping the 128-row tiles that share input rows (the 3 x 3 taps of neighbouring pixels) sit on 8 different L2s
 // and each XCD streams nearly the whole image.  Here XCD x owns a CONTIGUOUS run of tiles (the column tiles of one row tile
@@ -1395,6 +1436,26 @@ int gemm_conv3d_bf16x3(const Conv3dA& A, const void* packed, int N, const Epilog
     const unsigned gm = (unsigned)((L.M + G2_BM - 1) / G2_BM);
     if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<Conv3dLoader, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
     else hipLaunchKernelGGL((gemm_tile_bf3<Conv3dLoader, 64>), dim3(gm, 1u), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+// sparse convolution by rulebook (gemm.h): the general bf16x3 tile kernel behind SparseConvLoader
+int gemm_sparse_conv_bf16x3(const SparseConvA& A, int64_t M, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc,
+                            hipStream_t st) {
+    if (!A.in || !A.rule || !packed || !C || N <= 0 || M < 0 || A.taps <= 0 || A.taps > 64 || A.cp <= 0 || A.k2 < 0 ||
+        (A.k2 > 0 && !A.a2) || A.in_rows < 0 || A.in_rows > 0x7fffffffll || ep.res_gather || ep.ps)
+        return ML3D_E_INVALID;
+    if ((A.cp % BF_KC) != 0 || (A.k2 % BF_KC) != 0 || A.ldi < A.cp || (A.ldi & 3) != 0 || (((uintptr_t)A.in) & 15) != 0 ||
+        (A.k2 > 0 && (A.lda2 < A.k2 || (A.lda2 & 3) != 0 || (((uintptr_t)A.a2) & 15) != 0)))
+        return ML3D_E_UNSUPPORTED;
+    if (M == 0) return 0;
+    SparseConvLoader L;
+    L.A = A; L.M = M; L.K = A.taps * A.cp + A.k2;
+    if (A.k2 == 0) L.A.a2 = nullptr;
+    const int Npad = bf3_npad(N);
+    const unsigned gm = (unsigned)((M + G2_BM - 1) / G2_BM);
+    if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<SparseConvLoader, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
+    else hipLaunchKernelGGL((gemm_tile_bf3<SparseConvLoader, 64>), dim3(gm, 1u), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 

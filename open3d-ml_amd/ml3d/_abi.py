@@ -98,6 +98,7 @@ SYMBOLS = [
     "ml3d_pt_interpolate",
     "ml3d_pvcnn_voxel_coords", "ml3d_avg_voxelize_workspace_bytes", "ml3d_avg_voxelize", "ml3d_conv3d_ndhwc_bf16x3",
     "ml3d_trilinear_devoxelize", "ml3d_segment_max_rows_workspace_bytes", "ml3d_segment_max_rows",
+    "ml3d_scn_build_workspace_bytes", "ml3d_scn_build", "ml3d_sparse_conv_bf16x3", "ml3d_scn_bn_relu",
 ]
 
 
@@ -308,6 +309,14 @@ def bind(lib):
     lib.ml3d_segment_max_rows_workspace_bytes.argtypes = [i64, i64, i32]
     lib.ml3d_segment_max_rows.restype = C.c_int
     lib.ml3d_segment_max_rows.argtypes = [vp, i64, i64, i64, i32, vp, i64, vp, sz, vp]
+    lib.ml3d_scn_build_workspace_bytes.restype = sz
+    lib.ml3d_scn_build_workspace_bytes.argtypes = [i64, i32]
+    lib.ml3d_scn_build.restype = C.c_int
+    lib.ml3d_scn_build.argtypes = [vp, vp, i64, i32, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]
+    lib.ml3d_sparse_conv_bf16x3.restype = C.c_int
+    lib.ml3d_sparse_conv_bf16x3.argtypes = [vp, i64, i64, i32, vp, i32, i64, vp, i64, i32, vp, i32, vp, vp, i64, i32, f32, vp, i64, vp]
+    lib.ml3d_scn_bn_relu.restype = C.c_int
+    lib.ml3d_scn_bn_relu.argtypes = [vp, i64, i64, i32, vp, vp, vp, i64, vp]
     lib.ml3d_vote_update.restype = C.c_int
     lib.ml3d_vote_update.argtypes = [vp, vp, i64, i32, f32, vp, i64, vp]
     lib.ml3d_argmax_labels.restype = C.c_int

@@ -23,3 +23,4 @@ from .train import (gemm_tn, LinearFunction, BatchNormActFunction, batch_norm_ac
 from .pointtransformer import furthest_point_sampling, pt_attention, pt_transition_down, pt_interpolate   # noqa: F401
 from .pvcnn import (pvcnn_voxel_coords, avg_voxelize, pack_conv3d_weights, conv3d_ndhwc, trilinear_devoxelize,   # noqa: F401
                     segment_max_rows, linear_rows_bf16x3)
+from .sparseconv import ScnPyramid, scn_build, pack_sparse_weights, sparse_conv, scn_bn_relu   # noqa: F401

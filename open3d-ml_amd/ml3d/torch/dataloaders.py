@@ -134,6 +134,45 @@ class PointTransformerBatch:
         return self
 
 
+class SparseConvUnetBatch:
+    """concat_batcher.py:407-452: one entry per cloud in the lists ``point`` / ``feat`` / ``label``, the cloud sizes in
+    ``batch_lengths`` (the model concatenates them itself and keeps the row splits on the host)."""
+
+    def __init__(self, batches):
+        self.point, self.feat, self.label, self.batch_lengths = [], [], [], []
+        for batch in batches:
+            data = batch['data']
+            self.point.append(torch.as_tensor(data['point'], dtype=torch.float32))
+            self.feat.append(torch.as_tensor(data['feat'], dtype=torch.float32))
+            self.label.append(torch.as_tensor(data['label']))
+            self.batch_lengths.append(int(self.point[-1].shape[0]))
+
+    def pin_memory(self):
+        self.point = [t.pin_memory() for t in self.point]
+        self.feat = [t.pin_memory() for t in self.feat]
+        self.label = [t.pin_memory() for t in self.label]
+        return self
+
+    def to(self, device):
+        self.point = [t.to(device, non_blocking=True) for t in self.point]
+        self.feat = [t.to(device, non_blocking=True) for t in self.feat]
+        self.label = [t.to(device, non_blocking=True) for t in self.label]
+        return self
+
+    @staticmethod
+    def scatter(batch, num_gpu):
+        size = len(batch.batch_lengths)
+        per = -(-size // num_gpu)
+        out = []
+        for i in range(num_gpu):
+            sl = slice(per * i, min(per * (i + 1), size))
+            b = SparseConvUnetBatch([])
+            b.point, b.feat, b.label, b.batch_lengths = batch.point[sl], batch.feat[sl], batch.label[sl], batch.batch_lengths[sl]
+            if len(b.point):
+                out.append(b)
+        return out
+
+
 class ConcatBatcher(object):
 
     def __init__(self, device, model='KPConv'):
@@ -147,8 +186,10 @@ class ConcatBatcher(object):
             return ObjectDetectBatch(batches)
         if self.model == "PointTransformer":
             return {'data': PointTransformerBatch(batches), 'attr': []}
+        if self.model == "SparseConvUnet":
+            return {'data': SparseConvUnetBatch(batches), 'attr': {}}
         raise Exception("ConcatBatcher (MI355X build): model '%s' is outside the hot path (KPFCNN, PointPillars, "
-                        "PointTransformer)" % self.model)
+                        "PointTransformer, SparseConvUnet)" % self.model)
 
     def _kpconv(self, batches):
         from .models.kpconv import KPConvBatch

@@ -1,7 +1,7 @@
 """``open3d.ml.torch`` — ``ops`` and ``layers`` (native, this repository); with ``OPEN3D_ML_ROOT`` also the checkout's
 torch side (``models``, ``modules``, ``pipelines``, ``dataloaders``) exactly as upstream's ``open3d/ml/torch/__init__.py``
 re-exports it — with ONE change: the three inference hot-path models (``RandLANet``, ``KPFCNN``, ``PointPillars``) and the
-``PointTransformer`` and ``PVCNN`` extensions of this repository are registered over the checkout's in ``ml3d.utils``'s MODEL registry, so
+``PointTransformer``, ``PVCNN`` and ``SparseConvUnet`` extensions of this repository are registered over the checkout's in ``ml3d.utils``'s MODEL registry, so
 ``get_module("model", "RandLANet", "torch")`` (``scripts/run_pipeline.py:129-132``) returns the MI355X-native class.
 Set ``ML3D_AMD_KEEP_REFERENCE_MODELS=1`` to leave the registry alone (the reference's PyTorch forwards then run on the
 native ops only)."""
@@ -48,7 +48,8 @@ if _checkout():
 
         KPFCNN.__module__ = native.KPFCNN.__module__
         KPFCNN.__qualname__ = "KPFCNN"
-        for cls in (native.RandLANet, KPFCNN, native.PointPillars, native.PointTransformer, native.PVCNN):
+        for cls in (native.RandLANet, KPFCNN, native.PointPillars, native.PointTransformer, native.PVCNN,
+                    native.SparseConvUnet):
             MODEL._register_module(cls, "torch")
             setattr(models, cls.__name__, cls)
 

@@ -46,7 +46,9 @@ class KNNSearch(torch.nn.Module):
 
 
 class _OutOfScopeLayer(torch.nn.Module):
-    """Import target of the reference's out-of-scope SparseConvNet (``sparseconvnet.py:9``): constructing it raises."""
+    """Import target of the reference's own ``sparseconvnet.py:9``: constructing it raises.  Live sparse convolutions for
+    arbitrary positions stay outside this repository's scope; the native ``SparseConvUnet`` class (registered over the
+    checkout's) does not go through these layers -- it calls ``ml3d.ops.scn_build`` / ``ml3d.ops.sparse_conv`` directly."""
 
     def __init__(self, *args, **kwargs):
         super().__init__()

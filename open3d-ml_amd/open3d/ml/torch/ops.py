@@ -79,14 +79,14 @@ def _out_of_scope(name):
     def fn(*args, **kwargs):
         raise NotImplementedError("open3d.ml.torch.ops.%s belongs to a model or a training path outside this repository's scope "
                                   "(SURVEY.md §2: PointRCNN / SparseConvNet; the reference's own PVCNN forward -- the native "
-                                  "PVCNN class calls ml3d.ops.trilinear_devoxelize directly); only its import target exists" % name)
+                                  "PVCNN and SparseConvUnet classes call ml3d.ops directly); only its import target exists" % name)
     fn.__name__ = name
     return fn
 
 
 # import targets of the reference's out-of-scope models (ml3d/torch/models/{sparseconvnet,point_rcnn}.py,
-# ml3d/torch/utils/{pointnet,roipool3d}) and of the reference's own pvcnn.py (served by the native PVCNN class, which does not
-# go through these): resolvable so that `import ml3d.torch.models` works, inert otherwise
+# ml3d/torch/utils/{pointnet,roipool3d}) and of the reference's own pvcnn.py / sparseconvnet.py (served by the native PVCNN and
+# SparseConvUnet classes, which call ml3d.ops directly and do not go through these): resolvable so that `import ml3d.torch.models` works, inert otherwise
 for _n in ("reduce_subarrays_sum", "roi_pool", "three_nn", "three_interpolate",
            "three_interpolate_grad", "ball_query", "trilinear_devoxelize_forward", "trilinear_devoxelize_backward",
            "continuous_conv", "sparse_conv", "sparse_conv_transpose", "invert_neighbors_list", "build_spatial_hash_table"):
