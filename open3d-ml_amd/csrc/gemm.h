@@ -40,6 +40,27 @@ struct Epilogue {
     // rg_limit: gathered rows outside [0, rg_limit) contribute nothing (the shadow neighbour of a point with no coarse point
     // in reach); must be set whenever res_gather is
     int64_t rg_stride, rg_limit;
+
+    // Named construction (the struct stays an aggregate passed to kernels by value: the fields above keep their order, and
+    // `Epilogue{}` is the raw epilogue -- no bias, no activation, row-major store).  Start from of() and chain what applies.
+    static Epilogue of(const float* bias, int act, float slope) {
+        Epilogue e{};
+        e.bias = bias; e.act = act; e.slope = slope;
+        return e;
+    }
+    Epilogue& residual_rows(const float* r, int64_t ld) { residual = r; ldr = ld; return *this; }
+    Epilogue& pixel_shuffle(int stride, int h, int w, int cout) { ps = stride; ps_h = h; ps_w = w; ps_cout = cout; return *this; }
+    Epilogue& second_bias(const float* b) { bias2 = b; return *this; }
+    // residual row = (m / rows_per_item) * src_rows_per_item + idx[m * stride]; see the fields.  Needs residual_rows()
+    Epilogue& gathered_residual(const int32_t* idx, int64_t stride, int64_t limit, int64_t rows_per_item, int64_t src_rows_per_item) {
+        res_gather = idx; rg_stride = stride; rg_limit = limit;
+        rg_rows_per_item = rows_per_item; rg_src_rows_per_item = src_rows_per_item;
+        return *this;
+    }
+    // global row indices: one "item" spanning every row
+    Epilogue& gathered_residual(const int32_t* idx, int64_t stride, int64_t limit) {
+        return gathered_residual(idx, stride, limit, (int64_t)1 << 62, 0);
+    }
 };
 
 // dense / gathered / concatenated rows

@@ -29,6 +29,43 @@ __device__ __forceinline__ float gm_act(float v, int act, float slope) {
     return v;
 }
 
+// ---- epilogue slow path: the pieces gemm_tile, tile2_epilogue and gemm_reduce share --------------------------------------
+// pixel-shuffle store (Epilogue::ps): column col = (dy, dx, co), row m = input pixel (b, y, x) -> element offset of (output pixel,
+// co) in C.  The column's part is split off so that the tile kernels pay its divisions once per column, not per element
+struct PsCol { int co, dy, dx; };
+__device__ __forceinline__ PsCol ps_col(int col, const Epilogue& ep) {
+    PsCol c;
+    c.co = col % ep.ps_cout;
+    const int dd = col / ep.ps_cout;
+    c.dy = dd / ep.ps; c.dx = dd % ep.ps;
+    return c;
+}
+__device__ __forceinline__ int64_t ps_offset(int64_t m, const PsCol& c, const Epilogue& ep, int64_t ldc) {
+    const int x = (int)(m % ep.ps_w);
+    const int64_t t = m / ep.ps_w;
+    const int y = (int)(t % ep.ps_h);
+    const int64_t bi = t / ep.ps_h;
+    const int64_t opix = (bi * ep.ps_h * ep.ps + (int64_t)y * ep.ps + c.dy) * ((int64_t)ep.ps_w * ep.ps) + (int64_t)x * ep.ps + c.dx;
+    return opix * ldc + c.co;
+}
+
+// v + the residual of output element (m, col), gathered when ep.res_gather is set.  The item of row m comes from the caller: the
+// tile kernels fix it once per tile (rg_base = source row base of the tile's FIRST row's item, rg_l = m's distance from that item's
+// first row; a tile crosses items at most once), gemm_reduce passes the row's own item base and rg_l = 0
+__device__ __forceinline__ float add_residual(float v, const Epilogue& ep, int64_t m, int col, int64_t rg_base, int64_t rg_l) {
+    if (ep.residual) {
+        int64_t rr = m;
+        bool take = true;
+        if (ep.res_gather) {
+            const int64_t g = ep.res_gather[ep.rg_stride ? m * ep.rg_stride : m];
+            take = g >= 0 && g < ep.rg_limit;
+            rr = rg_base + (rg_l >= ep.rg_rows_per_item ? ep.rg_src_rows_per_item : 0) + g;
+        }
+        if (take) v += ep.residual[rr * ep.ldr + col];
+    }
+    return v;
+}
+
 // ---- epilogue fast path -------------------------------------------------------------------------------------------------
 // The plain epilogue (bias [+ bias2] [+ residual] + activation, row-major C) is the whole kernel for shallow K: RandLA's and
 // KPConv's Linears have K = 32 .. 128 (1-4 chunks), and the generic store -- a 64-bit m * ldc + col, a bounds test and the
@@ -331,20 +368,12 @@ gemm_tile(Loader L, const float* __restrict__ Bm, int N, int bvec, Epilogue ep, 
         return;
     }
     if (ep.ps > 0) {
-        const int co = col % ep.ps_cout, dd = col / ep.ps_cout;
-        const int dy = dd / ep.ps, dx = dd % ep.ps;
-        const float b = ep.bias ? ep.bias[co] : 0.f;
+        const PsCol pc = ps_col(col, ep);
+        const float b = ep.bias ? ep.bias[pc.co] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int64_t m = m0 + rt * 32 + mfma32_row(r, hi);
-            if (m < L.M) {
-                const int x = (int)(m % ep.ps_w);
-                const int64_t t = m / ep.ps_w;
-                const int y = (int)(t % ep.ps_h);
-                const int64_t bi = t / ep.ps_h;
-                const int64_t opix = (bi * ep.ps_h * ep.ps + (int64_t)y * ep.ps + dy) * ((int64_t)ep.ps_w * ep.ps) + (int64_t)x * ep.ps + dx;
-                C[opix * ldc + co] = gm_act(acc[r] + b, ep.act, ep.slope);
-            }
+            if (m < L.M) C[ps_offset(m, pc, ep, ldc)] = gm_act(acc[r] + b, ep.act, ep.slope);
         }
         return;
     }
@@ -369,20 +398,7 @@ gemm_tile(Loader L, const float* __restrict__ Bm, int N, int bvec, Epilogue ep, 
     for (int r = 0; r < 16; ++r) {
         const int lr = rt * 32 + mfma32_row(r, hi);
         const int64_t m = m0 + lr;
-        if (m < L.M) {
-            float v = acc[r] + b;
-            if (ep.residual) {
-                int64_t rr = m;
-                bool take = true;
-                if (ep.res_gather) {
-                    const int64_t g = ep.res_gather[ep.rg_stride ? m * ep.rg_stride : m];
-                    take = g >= 0 && g < ep.rg_limit;
-                    rr = rg_base + (rg_l0 + lr >= ep.rg_rows_per_item ? ep.rg_src_rows_per_item : 0) + g;
-                }
-                if (take) v += ep.residual[rr * ep.ldr + col];
-            }
-            C[m * ldc + col] = gm_act(v, ep.act, ep.slope);
-        }
+        if (m < L.M) C[m * ldc + col] = gm_act(add_residual(acc[r] + b, ep, m, col, rg_base, rg_l0 + lr), ep.act, ep.slope);
     }
 }
 
@@ -416,22 +432,14 @@ __device__ __forceinline__ void tile2_epilogue(f32x16 (&acc)[RT][CT], const Epil
         const int col = n0 + wc * (32 * CT) + 32 * j + cl;
         if (col >= N) continue;
         if (ep.ps > 0) {
-            const int co = col % ep.ps_cout, dd = col / ep.ps_cout;
-            const int dy = dd / ep.ps, dx = dd % ep.ps;
-            const float b = ep.bias ? ep.bias[co] : 0.f;
+            const PsCol pc = ps_col(col, ep);
+            const float b = ep.bias ? ep.bias[pc.co] : 0.f;
 #pragma unroll
             for (int i = 0; i < RT; ++i)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int64_t m = m0 + wr * 64 + i * 32 + mfma32_row(r, hi);
-                    if (m < M) {
-                        const int x = (int)(m % ep.ps_w);
-                        const int64_t t = m / ep.ps_w;
-                        const int y = (int)(t % ep.ps_h);
-                        const int64_t bi = t / ep.ps_h;
-                        const int64_t opix = (bi * ep.ps_h * ep.ps + (int64_t)y * ep.ps + dy) * ((int64_t)ep.ps_w * ep.ps) + (int64_t)x * ep.ps + dx;
-                        C[opix * ldc + co] = gm_act(acc[i][j][r] + b, ep.act, ep.slope);
-                    }
+                    if (m < M) C[ps_offset(m, pc, ep, ldc)] = gm_act(acc[i][j][r] + b, ep.act, ep.slope);
                 }
             continue;
         }
@@ -451,20 +459,7 @@ __device__ __forceinline__ void tile2_epilogue(f32x16 (&acc)[RT][CT], const Epil
             for (int r = 0; r < 16; ++r) {
                 const int lr = wr * 64 + i * 32 + mfma32_row(r, hi);
                 const int64_t m = m0 + lr;
-                if (m < M) {
-                    float v = acc[i][j][r] + b;
-                    if (ep.residual) {
-                        int64_t rr = m;
-                        bool take = true;
-                        if (ep.res_gather) {
-                            const int64_t g = ep.res_gather[ep.rg_stride ? m * ep.rg_stride : m];
-                            take = g >= 0 && g < ep.rg_limit;
-                            rr = rg_base + (rg_l0 + lr >= ep.rg_rows_per_item ? ep.rg_src_rows_per_item : 0) + g;
-                        }
-                        if (take) v += ep.residual[rr * ep.ldr + col];
-                    }
-                    C[m * ldc + col] = gm_act(v, ep.act, ep.slope);
-                }
+                if (m < M) C[m * ldc + col] = gm_act(add_residual(acc[i][j][r] + b, ep, m, col, rg_base, rg_l0 + lr), ep.act, ep.slope);
             }
     }
 }
@@ -663,7 +658,7 @@ __device__ __forceinline__ void xcd_tile(int& bx, int& by) {
     by = (int)(t - (unsigned)bx * gy);
 }
 
-template <class Loader, int BN, int KC, bool PF2>
+template <class Loader, int BN, int KC>
 __global__ void __launch_bounds__(256)
 gemm_tile2(Loader L, const float* __restrict__ Bm, int N, Epilogue ep, float* __restrict__ C, int64_t ldc) {
     constexpr int BP = BN + 4;
@@ -697,12 +692,10 @@ gemm_tile2(Loader L, const float* __restrict__ Bm, int N, Epilogue ep, float* __
     for (int j = 0; j < NROW; ++j) cx[j] = L.prepare(m0 + ar + ARS * j);
     const bool bcol_ok = n0 + bq + 3 < N;
 
-    // two register sets for the staged chunks: the loads of chunk c + 2 are issued before the MFMAs of chunk c, so they have
-    // TWO chunks of matrix time to land.  Measured on SECOND's 3x3 64 -> 64 conv (32-deep chunks, 64-column tiles): 0.353 ms
-    // against 0.328 ms with ONE set -- the extra registers cost more than the latency they hide -- so every instantiation the
-    // dispatcher uses today has PF2 = false; the path stays for wider tiles.
-    float4 ra0[NA4], rb0[NB4], ra1[PF2 ? NA4 : 1], rb1[PF2 ? NB4 : 1];
-    auto fetch = [&](float4* ra, float4* rb, int k0) {
+    // ONE register set for the staged chunk (a second set, chunk c + 2 requested before the MFMAs of chunk c, measured slower on
+    // SECOND's 3x3 64 -> 64 conv: 0.353 against 0.328 ms -- the extra registers cost more than the latency they hide)
+    float4 ra[NA4], rb[NB4];
+    auto fetch = [&](int k0) {
 #pragma unroll
         for (int j = 0; j < NA4; ++j) ra[j] = L.load4(cx[j], k0, aq);
 #pragma unroll
@@ -711,7 +704,7 @@ gemm_tile2(Loader L, const float* __restrict__ Bm, int N, Epilogue ep, float* __
             rb[j] = (bcol_ok && k < K) ? *reinterpret_cast<const float4*>(Bm + (int64_t)k * N + n0 + bq) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     };
-    auto stash = [&](const float4* ra, const float4* rb) {
+    auto stash = [&]() {
 #pragma unroll
         for (int j = 0; j < NA4; ++j) *reinterpret_cast<float4*>(As + (ar + ARS * j) * AP + aq) = ra[j];
 #pragma unroll
@@ -749,36 +742,16 @@ gemm_tile2(Loader L, const float* __restrict__ Bm, int N, Epilogue ep, float* __
         }
     };
 
-    fetch(ra0, rb0, 0);
-    stash(ra0, rb0);
+    fetch(0);
+    stash();
     block_sync_lds();
-    if constexpr (!PF2) {
-        for (int k0 = 0; k0 < K; k0 += KC) {
-            const bool more = k0 + KC < K;
-            if (more) fetch(ra0, rb0, k0 + KC);           // global loads in flight under the MFMAs
-            mfma_chunk();
-            block_sync_lds();
-            if (more) {
-                stash(ra0, rb0);
-                block_sync_lds();
-            }
-        }
-    } else {
-        if (KC < K) fetch(ra0, rb0, KC);                  // chunk 1 -> set 0
-        for (int k0 = 0; k0 < K; k0 += 2 * KC) {
-            // LDS holds chunk k0, set 0 chunk k0 + KC: request chunk k0 + 2 KC into set 1
-            if (k0 + 2 * KC < K) fetch(ra1, rb1, k0 + 2 * KC);
-            mfma_chunk();
-            block_sync_lds();
-            if (k0 + KC >= K) break;
-            stash(ra0, rb0);
-            block_sync_lds();
-            // LDS holds chunk k0 + KC, set 1 chunk k0 + 2 KC: request chunk k0 + 3 KC into set 0
-            if (k0 + 3 * KC < K) fetch(ra0, rb0, k0 + 3 * KC);
-            mfma_chunk();
-            block_sync_lds();
-            if (k0 + 2 * KC >= K) break;
-            stash(ra1, rb1);
+    for (int k0 = 0; k0 < K; k0 += KC) {
+        const bool more = k0 + KC < K;
+        if (more) fetch(k0 + KC);           // global loads in flight under the MFMAs
+        mfma_chunk();
+        block_sync_lds();
+        if (more) {
+            stash();
             block_sync_lds();
         }
     }
@@ -931,8 +904,7 @@ gemm_tile_bf3(Loader L, const u32x4* __restrict__ Bp, int N, int Npad, Epilogue 
         }
     }
     if (partial) {
-        const Epilogue raw = {nullptr, nullptr, 0, 0, 0.f, 0, 0, 0, 0};
-        tile2_epilogue<RT, CT>(acc, raw, partial + (int64_t)blockIdx.z * L.M * N, N, L.M, N, m0, n0, wr, wc, hi, cl);
+        tile2_epilogue<RT, CT>(acc, Epilogue{}, partial + (int64_t)blockIdx.z * L.M * N, N, L.M, N, m0, n0, wr, wc, hi, cl);
         return;
     }
     tile2_epilogue<RT, CT>(acc, ep, C, ldc, L.M, N, m0, n0, wr, wc, hi, cl);
@@ -1144,29 +1116,16 @@ __global__ void gemm_reduce(const float* __restrict__ partial, int splits, int64
         float v = 0.f;
         for (int z = 0; z < splits; ++z) v += partial[(int64_t)z * total + i];
         if (ep.ps > 0) {
-            const int co = col % ep.ps_cout, dd = col / ep.ps_cout;
-            const int dy = dd / ep.ps, dx = dd % ep.ps;
-            if (ep.bias) v += ep.bias[co];
-            const int x = (int)(m % ep.ps_w);
-            const int64_t t = m / ep.ps_w;
-            const int y = (int)(t % ep.ps_h);
-            const int64_t bi = t / ep.ps_h;
-            const int64_t opix = (bi * ep.ps_h * ep.ps + (int64_t)y * ep.ps + dy) * ((int64_t)ep.ps_w * ep.ps) + (int64_t)x * ep.ps + dx;
-            C[opix * ldc + co] = gm_act(v, ep.act, ep.slope);
+            const PsCol pc = ps_col(col, ep);
+            if (ep.bias) v += ep.bias[pc.co];
+            C[ps_offset(m, pc, ep, ldc)] = gm_act(v, ep.act, ep.slope);
             continue;
         }
-        if (ep.bias) v += ep.bias2 ? ep.bias[col] + ep.bias2[col] : ep.bias[col];
-        if (ep.residual) {
-            int64_t rr = m;
-            bool take = true;
-            if (ep.res_gather) {
-                const int64_t g = ep.res_gather[ep.rg_stride ? m * ep.rg_stride : m];
-                take = g >= 0 && g < ep.rg_limit;
-                rr = (m < ep.rg_rows_per_item ? 0 : m / ep.rg_rows_per_item) * ep.rg_src_rows_per_item + g;
-            }
-            if (take) v += ep.residual[rr * ep.ldr + col];
-        }
-        C[m * ldc + col] = gm_act(v, ep.act, ep.slope);
+        // (the tile kernels' rule and order: bias, then bias2, each if set)
+        float b = ep.bias ? ep.bias[col] : 0.f;
+        if (ep.bias2) b += ep.bias2[col];
+        const int64_t rg_base = ep.res_gather ? (m < ep.rg_rows_per_item ? 0 : m / ep.rg_rows_per_item) * ep.rg_src_rows_per_item : 0;
+        C[m * ldc + col] = gm_act(add_residual(v + b, ep, m, col, rg_base, 0), ep.act, ep.slope);
     }
 }
 
@@ -1214,18 +1173,27 @@ static int big_bn(int64_t M, int N, int K, const float* Bm, const Epilogue& ep) 
     return 0;
 }
 
+// sum the split-K partials and apply the epilogue (the f32 and the bf16x3 path)
+static int launch_reduce(const float* partial, int splits, int64_t M, int N, const Epilogue& ep, float* C, int64_t ldc,
+                         hipStream_t st) {
+    const int64_t total = M * N;
+    const unsigned nb = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(gemm_reduce, dim3(nb), dim3(256), 0, st, partial, splits, M, N, ep, C, ldc);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
 template <class L2>
 static void launch_big(const L2& L, const float* Bm, int N, int bn, int kc, const Epilogue& ep, float* C, int64_t ldc,
                        hipStream_t st) {
     const unsigned gm = (unsigned)((L.M + G2_BM - 1) / G2_BM);
     if (bn == 128) {
         const dim3 g(gm, (unsigned)((N + 127) / 128));
-        if (kc == 64) hipLaunchKernelGGL((gemm_tile2<L2, 128, 64, false>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
-        else hipLaunchKernelGGL((gemm_tile2<L2, 128, 32, false>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
+        if (kc == 64) hipLaunchKernelGGL((gemm_tile2<L2, 128, 64>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
+        else hipLaunchKernelGGL((gemm_tile2<L2, 128, 32>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
     } else {
         const dim3 g(gm, (unsigned)((N + 63) / 64));
-        if (kc == 64) hipLaunchKernelGGL((gemm_tile2<L2, 64, 64, false>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
-        else hipLaunchKernelGGL((gemm_tile2<L2, 64, 32, false>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
+        if (kc == 64) hipLaunchKernelGGL((gemm_tile2<L2, 64, 64>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
+        else hipLaunchKernelGGL((gemm_tile2<L2, 64, 32>), g, dim3(256), 0, st, L, Bm, N, ep, C, ldc);
     }
 }
 
@@ -1299,13 +1267,7 @@ static int gemm_launch(const Loader& L, const float* Bm, int N, const Epilogue& 
     else if (gemm_depth(grid) == 1) hipLaunchKernelGGL((gemm_tile<Loader, false, 1>), grid, dim3(256), 0, st, L, Bm, N, bvec, ep, C, ldc, kper, partial);
     else hipLaunchKernelGGL((gemm_tile<Loader, false, 2>), grid, dim3(256), 0, st, L, Bm, N, bvec, ep, C, ldc, kper, partial);
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    if (splits > 1) {
-        int64_t total = M * N;
-        unsigned nb = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(gemm_reduce, dim3(nb), dim3(256), 0, st, partial, splits, M, N, ep, C, ldc);
-        if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    }
-    return 0;
+    return splits > 1 ? launch_reduce(partial, splits, M, N, ep, C, ldc, st) : 0;
 }
 
 // ---- bf16x3 convolution ------------------------------------------------------------------------------------------------
@@ -1357,6 +1319,22 @@ static int bf3_splits(int64_t M, int N, int K) {
     return s < 1 ? 1 : (int)s;
 }
 
+// The one launch of gemm_tile_bf3: 128-row tiles, 128- or 64-column tiles by N, K cut into `splits` slices of whole chunks whose
+// partials (partial_ws: splits * M * N floats) gemm_reduce sums; splits == 1 applies the epilogue in the kernel
+template <class Loader>
+static int launch_bf3(const Loader& L, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc, int splits,
+                      void* partial_ws, hipStream_t st) {
+    const int kper = ((L.K + splits - 1) / splits + BF_KC - 1) / BF_KC * BF_KC;
+    splits = (L.K + kper - 1) / kper;
+    float* partial = splits > 1 ? (float*)partial_ws : nullptr;
+    const int bn = N > 64 ? 128 : 64;
+    const dim3 grid((unsigned)((L.M + G2_BM - 1) / G2_BM), (unsigned)((N + bn - 1) / bn), (unsigned)splits);
+    hipLaunchKernelGGL((N > 64 ? gemm_tile_bf3<Loader, 128> : gemm_tile_bf3<Loader, 64>), grid, dim3(256), 0, st, L,
+                       (const u32x4*)packed, N, bf3_npad(N), ep, C, ldc, kper, partial);
+    if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
+    return splits > 1 ? launch_reduce(partial, splits, L.M, N, ep, C, ldc, st) : 0;
+}
+
 size_t gemm_partial_bytes_bf16x3(int64_t M, int N, int K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     const int s = bf3_splits(M, N, K);
@@ -1375,23 +1353,9 @@ int gemm_rows_bf16x3(const float* a, int64_t lda, int k1, const float* a2, int64
     if (M == 0) return 0;
     RowsLoader2 L;
     L.a = a; L.lda = lda; L.a2 = k2 > 0 ? a2 : nullptr; L.lda2 = lda2; L.k1 = k1; L.M = M; L.K = K;
-    const int Npad = bf3_npad(N);
     int splits = bf3_splits(M, N, K);
     if (splits > 1 && (!partial_ws || partial_bytes < sizeof(float) * (size_t)splits * (size_t)M * (size_t)N)) splits = 1;
-    int kper = ((K + splits - 1) / splits + BF_KC - 1) / BF_KC * BF_KC;
-    splits = (K + kper - 1) / kper;
-    float* partial = splits > 1 ? (float*)partial_ws : nullptr;
-    const unsigned gm = (unsigned)((M + G2_BM - 1) / G2_BM);
-    if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<RowsLoader2, 128>), dim3(gm, (unsigned)((N + 127) / 128), (unsigned)splits), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, kper, partial);
-    else hipLaunchKernelGGL((gemm_tile_bf3<RowsLoader2, 64>), dim3(gm, 1u, (unsigned)splits), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, kper, partial);
-    if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    if (splits > 1) {
-        const int64_t total = M * N;
-        const unsigned nb = (unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-        hipLaunchKernelGGL(gemm_reduce, dim3(nb), dim3(256), 0, st, partial, splits, M, N, ep, C, ldc);
-        if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    }
-    return 0;
+    return launch_bf3(L, packed, N, ep, C, ldc, splits, partial_ws, st);
 }
 
 int gemm_conv_bf16x3(const ConvA& A, const void* packed, int N, const Epilogue& ep, float* C, int64_t ldc, hipStream_t st) {
@@ -1399,8 +1363,6 @@ int gemm_conv_bf16x3(const ConvA& A, const void* packed, int N, const Epilogue& 
     ConvLoader2 L2;
     L2.A = A; L2.M = (int64_t)A.B * A.OH * A.OW; L2.K = A.KH * A.KW * A.C;
     if (L2.M <= 0) return 0;
-    const int Npad = bf3_npad(N);
-    const unsigned gm = (unsigned)((L2.M + G2_BM - 1) / G2_BM);
     // 3 x 3 / stride 1 / pad 1 (13 of SECOND's 16 convolutions): the window-staged kernel.  (Only the HOST EMULATOR build of the tests
     // reads ML3D_CONV_WINDOW, once, so that its suites can push these shapes through the general kernel as well.)
 #ifdef ML3D_TEST_HOOKS
@@ -1410,14 +1372,14 @@ int gemm_conv_bf16x3(const ConvA& A, const void* packed, int N, const Epilogue& 
 #endif
     if (window && A.KH == 3 && A.KW == 3 && A.stride == 1 && A.pad == 1 && A.OH == A.H && A.OW == A.W &&
         (int64_t)A.B * A.H * A.W * A.C < 0x7fffffffll) {
-        Conv3Args a3 = {A.in, A.H, A.W, A.C, L2.M};
-        if (N > 64) hipLaunchKernelGGL((conv3x3s1_bf3<128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, a3, (const u32x4*)packed, N, Npad, ep, C, ldc);
-        else hipLaunchKernelGGL((conv3x3s1_bf3<64>), dim3(gm, 1u), dim3(256), 0, st, a3, (const u32x4*)packed, N, Npad, ep, C, ldc);
+        const Conv3Args a3 = {A.in, A.H, A.W, A.C, L2.M};
+        const int bn = N > 64 ? 128 : 64;
+        const dim3 grid((unsigned)((L2.M + G2_BM - 1) / G2_BM), (unsigned)((N + bn - 1) / bn));
+        hipLaunchKernelGGL((N > 64 ? conv3x3s1_bf3<128> : conv3x3s1_bf3<64>), grid, dim3(256), 0, st, a3, (const u32x4*)packed, N,
+                           bf3_npad(N), ep, C, ldc);
         return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
     }
-    if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<ConvLoader2, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L2, (const u32x4*)packed, N, Npad, ep, C, ldc, L2.K, (float*)nullptr);
-    else hipLaunchKernelGGL((gemm_tile_bf3<ConvLoader2, 64>), dim3(gm, 1u), dim3(256), 0, st, L2, (const u32x4*)packed, N, Npad, ep, C, ldc, L2.K, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+    return launch_bf3(L2, packed, N, ep, C, ldc, 1, nullptr, st);
 }
 
 // 3 x 3 x 3 / stride 1 / pad 1 on a channels-last volume (gemm.h): the general bf16x3 tile kernel behind Conv3dLoader
@@ -1432,11 +1394,7 @@ int gemm_conv3d_bf16x3(const Conv3dA& A, const void* packed, int N, const Epilog
     if (!gemm_conv3d_bf16x3_ok(A) || !packed || !C || N <= 0 || ep.res_gather || ep.ps) return ML3D_E_INVALID;
     Conv3dLoader L;
     L.A = A; L.M = (int64_t)A.B * A.D * A.H * A.W; L.K = 27 * A.C;
-    const int Npad = bf3_npad(N);
-    const unsigned gm = (unsigned)((L.M + G2_BM - 1) / G2_BM);
-    if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<Conv3dLoader, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
-    else hipLaunchKernelGGL((gemm_tile_bf3<Conv3dLoader, 64>), dim3(gm, 1u), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+    return launch_bf3(L, packed, N, ep, C, ldc, 1, nullptr, st);
 }
 
 // sparse convolution by rulebook (gemm.h): the general bf16x3 tile kernel behind SparseConvLoader
@@ -1452,11 +1410,7 @@ int gemm_sparse_conv_bf16x3(const SparseConvA& A, int64_t M, const void* packed,
     SparseConvLoader L;
     L.A = A; L.M = M; L.K = A.taps * A.cp + A.k2;
     if (A.k2 == 0) L.A.a2 = nullptr;
-    const int Npad = bf3_npad(N);
-    const unsigned gm = (unsigned)((M + G2_BM - 1) / G2_BM);
-    if (N > 64) hipLaunchKernelGGL((gemm_tile_bf3<SparseConvLoader, 128>), dim3(gm, (unsigned)((N + 127) / 128)), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
-    else hipLaunchKernelGGL((gemm_tile_bf3<SparseConvLoader, 64>), dim3(gm, 1u), dim3(256), 0, st, L, (const u32x4*)packed, N, Npad, ep, C, ldc, L.K, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+    return launch_bf3(L, packed, N, ep, C, ldc, 1, nullptr, st);
 }
 
 int gemm_rows(const RowsA& A, const float* Bm, int64_t M, int N, int K, const Epilogue& ep, float* C, int64_t ldc,

@@ -88,6 +88,10 @@ int scan_inclusive_i32(int* a, int64_t n, int* block_sums, hipStream_t stream);
 // HIP graph uses instead of hipMemsetAsync (ROCm 7.2: a graph's memset node did not clear its target on later replays, grid.hip)
 void zero_async(void* ptr, size_t bytes, hipStream_t stream);
 
+// a caller's workspace from its first 256-byte boundary on (null stays null), and what is left of `bytes` whatever the alignment cost
+static inline char* ws_align(void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
+static inline size_t ws_avail(const void* ws, size_t bytes) { return ws && bytes > 256 ? bytes - 256 : 0; }
+
 // order-preserving float <-> uint so atomicMin/atomicMax work on floats
 __device__ __forceinline__ unsigned f2ord(float f) {
     unsigned u = __float_as_uint(f);

@@ -875,7 +875,7 @@ static int kpconv_run(const float* q_pts, const float* s_pts, const int32_t* nei
         return ML3D_E_INVALID;
     if (workspace_bytes < ml3d_kpconv_workspace_bytes(n_queries, cin, cout, num_kernel_points)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    char* p = ws_align(workspace);
     float* wf = (float*)p;
     p += kp_align(sizeof(float) * (size_t)n_queries * KP_K * (size_t)cin);
     KpArgs a;
@@ -913,7 +913,7 @@ static int kpconv_run(const float* q_pts, const float* s_pts, const int32_t* nei
     A.gather = nullptr; A.gather_stride = 0; A.a_rows = n_queries;
     A.a2 = nullptr; A.lda2 = 0; A.k2 = 0;
     A.gather_on_a2 = 0; A.g_rows_per_item = 0; A.g_src_rows_per_item = 0;
-    Epilogue ep = {bias, nullptr, 0, act, slope, 0, 0, 0, 0};
+    const Epilogue ep = Epilogue::of(bias, act, slope);
     if (packed) {           // the contraction on the bf16 matrix pipe (gemm.h: three-way split of both operands); ineligible -> f32 below
         const int rcb = gemm_rows_bf16x3(wf, (int64_t)KP_K * cin, KP_K * cin, nullptr, 0, 0, n_queries, packed, cout, ep, out, cout, p,
                                          gemm_partial_bytes_bf16x3(n_queries, cout, KP_K * cin), st);
@@ -1053,36 +1053,6 @@ extern "C" int ml3d_kpconv_deformable(const float* q_pts, const float* s_pts, co
     return kpconv_run(q_pts, s_pts, neighb_inds, n_queries, n_supports, max_neighbors, features, cin, kernel_points,
                       num_kernel_points, kp_extent, kp_influence_mode, offset_features, offset_dim, weights, bias, act, slope,
                       cout, out, workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t ml3d_linear_workspace_bytes(int64_t m, int n, int k) {
-    if (m < 0 || n <= 0 || k <= 0) return 0;
-    return gemm_partial_bytes(m, n, k) + 512;
-}
-
-extern "C" int ml3d_linear(const float* a, int64_t lda, int k1, const int32_t* a_gather, int64_t a_gather_stride,
-                           int64_t a_rows, const float* a2, int64_t lda2, int k2, const float* weights_t,
-                           const float* bias, const float* residual, int64_t ldr, const int32_t* residual_gather,
-                           int64_t residual_gather_stride, int64_t residual_rows, int act, float slope, float* out,
-                           int64_t ldc, int64_t m, int n, void* workspace, size_t workspace_bytes, void* stream) {
-    if (m < 0 || n <= 0 || k1 < 0 || k2 < 0 || k1 + k2 <= 0 || act < 0 || act > 2) return ML3D_E_INVALID;
-    if (m == 0) return 0;
-    if (!weights_t || !out || (k1 > 0 && !a) || (k2 > 0 && !a2) || lda < k1 || (k2 > 0 && lda2 < k2) || ldc < n ||
-        (residual && ldr < n) || (residual_gather && (!residual || residual_gather_stride < 1 || residual_rows < 0)))
-        return ML3D_E_INVALID;
-    RowsA A;
-    A.a = a; A.lda = lda; A.k1 = k1;
-    A.gather = a_gather; A.gather_stride = a_gather_stride; A.a_rows = a_rows;
-    A.a2 = a2; A.lda2 = lda2; A.k2 = k2;
-    A.gather_on_a2 = 0; A.g_rows_per_item = 0; A.g_src_rows_per_item = 0;
-    Epilogue ep = {bias, residual, ldr, act, slope, 0, 0, 0, 0};
-    if (residual_gather) {      // global row indices: one "item" spanning every row
-        ep.res_gather = residual_gather; ep.rg_rows_per_item = (int64_t)1 << 62; ep.rg_src_rows_per_item = 0;
-        ep.rg_stride = residual_gather_stride; ep.rg_limit = residual_rows;
-    }
-    char* p = workspace ? (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr;
-    size_t avail = workspace ? (workspace_bytes > 256 ? workspace_bytes - 256 : 0) : 0;
-    return gemm_rows(A, weights_t, m, n, k1 + k2, ep, out, ldc, p, avail, (hipStream_t)stream);
 }
 
 extern "C" int ml3d_gather_pool(const float* features, int64_t n_supports, int channels, const int32_t* inds,

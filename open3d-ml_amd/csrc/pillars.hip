@@ -334,22 +334,11 @@ extern "C" int ml3d_conv2d_nhwc(const float* in, int64_t batch, int h, int w, in
     A.OW = (w + 2 * pad - kw) / stride + 1;
     A.KH = kh; A.KW = kw; A.stride = stride; A.pad = pad;
     if (A.OH <= 0 || A.OW <= 0) return ML3D_E_INVALID;
-    Epilogue ep = {bias, nullptr, 0, act, slope, 0, 0, 0, 0};
-    char* p = workspace ? (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr;
-    size_t avail = workspace && workspace_bytes > 256 ? workspace_bytes - 256 : 0;
-    return gemm_conv(A, weights, cout, ep, out, out_pixel_stride, p, avail, (hipStream_t)stream);
+    return gemm_conv(A, weights, cout, Epilogue::of(bias, act, slope), out, out_pixel_stride, ws_align(workspace),
+                     ws_avail(workspace, workspace_bytes), (hipStream_t)stream);
 }
 
 // ---- the same convolution on the bf16 matrix pipe (gemm.h: three-way bf16 splits, float32-equivalent result) ---------------
-extern "C" size_t ml3d_gemm_pack_bf16x3_bytes(int k, int n) { return gemm_pack_bf16x3_bytes(k, n); }
-
-extern "C" int ml3d_gemm_pack_bf16x3(const float* weights, int k, int n, void* packed, size_t packed_bytes, void* stream) {
-    if (!weights || !packed || k <= 0 || n <= 0) return ML3D_E_INVALID;
-    if (k % 32) return ML3D_E_UNSUPPORTED;
-    if (packed_bytes < gemm_pack_bf16x3_bytes(k, n)) return ML3D_E_WORKSPACE;
-    return gemm_pack_bf16x3(weights, k, n, packed, (hipStream_t)stream);
-}
-
 extern "C" int ml3d_conv2d_nhwc_bf16x3(const float* in, int64_t batch, int h, int w, int cin, const void* packed,
                                        const float* bias, int kh, int kw, int stride, int pad, int act, float slope,
                                        int cout, float* out, int64_t out_pixel_stride, void* stream) {
@@ -363,8 +352,7 @@ extern "C" int ml3d_conv2d_nhwc_bf16x3(const float* in, int64_t batch, int h, in
     A.KH = kh; A.KW = kw; A.stride = stride; A.pad = pad;
     if (A.OH <= 0 || A.OW <= 0) return ML3D_E_INVALID;
     if (!gemm_conv_bf16x3_ok(A)) return ML3D_E_UNSUPPORTED;
-    Epilogue ep = {bias, nullptr, 0, act, slope, 0, 0, 0, 0};
-    return gemm_conv_bf16x3(A, packed, cout, ep, out, out_pixel_stride, (hipStream_t)stream);
+    return gemm_conv_bf16x3(A, packed, cout, Epilogue::of(bias, act, slope), out, out_pixel_stride, (hipStream_t)stream);
 }
 
 extern "C" int ml3d_deconv2d_nhwc(const float* in, int64_t batch, int h, int w, int cin, const float* weights,
@@ -378,11 +366,9 @@ extern "C" int ml3d_deconv2d_nhwc(const float* in, int64_t batch, int h, int w, 
     A.gather = nullptr; A.gather_stride = 0; A.a_rows = batch * h * w;
     A.a2 = nullptr; A.lda2 = 0; A.k2 = 0;
     A.gather_on_a2 = 0; A.g_rows_per_item = 0; A.g_src_rows_per_item = 0;
-    Epilogue ep = {bias, nullptr, 0, act, slope, stride, h, w, cout};
-    char* p = workspace ? (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr;
-    size_t avail = workspace && workspace_bytes > 256 ? workspace_bytes - 256 : 0;
-    return gemm_rows(A, weights, batch * h * w, stride * stride * cout, cin, ep, out, out_pixel_stride, p, avail,
-                     (hipStream_t)stream);
+    const Epilogue ep = Epilogue::of(bias, act, slope).pixel_shuffle(stride, h, w, cout);
+    return gemm_rows(A, weights, batch * h * w, stride * stride * cout, cin, ep, out, out_pixel_stride, ws_align(workspace),
+                     ws_avail(workspace, workspace_bytes), (hipStream_t)stream);
 }
 
 extern "C" int ml3d_deconv2d_nhwc_bf16x3(const float* in, int64_t batch, int h, int w, int cin, const void* packed,
@@ -391,43 +377,9 @@ extern "C" int ml3d_deconv2d_nhwc_bf16x3(const float* in, int64_t batch, int h, 
     if (batch <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || stride <= 0 || !in || !packed || !out ||
         out_pixel_stride < cout)
         return ML3D_E_INVALID;
-    Epilogue ep = {bias, nullptr, 0, act, slope, stride, h, w, cout};
+    const Epilogue ep = Epilogue::of(bias, act, slope).pixel_shuffle(stride, h, w, cout);
     return gemm_rows_bf16x3(in, cin, cin, nullptr, 0, 0, batch * h * w, packed, stride * stride * cout, ep, out, out_pixel_stride,
                             nullptr, 0, (hipStream_t)stream);
-}
-
-extern "C" size_t ml3d_linear_bf16x3_workspace_bytes(int64_t rows, int n, int k) { return gemm_partial_bytes_bf16x3(rows, n, k) + 512; }
-
-extern "C" int ml3d_linear_bf16x3(const float* a, int64_t lda, int k1, const float* a2, int64_t lda2, int k2, int64_t rows,
-                                  const void* packed, const float* bias, const float* residual, int64_t ldr, int n, int act,
-                                  float slope, float* out, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream) {
-    if (rows < 0 || k1 <= 0 || k2 < 0 || n <= 0 || lda < k1 || (k2 > 0 && (!a2 || lda2 < k2)) || ldc < n || !a || !packed || !out ||
-        act < 0 || act > 2 || (residual && ldr < n))
-        return ML3D_E_INVALID;
-    Epilogue ep = {bias, residual, ldr, act, slope, 0, 0, 0, 0};
-    char* p = workspace ? (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr;
-    const size_t avail = workspace && workspace_bytes > 256 ? workspace_bytes - 256 : 0;
-    return gemm_rows_bf16x3(a, lda, k1, a2, lda2, k2, rows, packed, n, ep, out, ldc, p, avail, (hipStream_t)stream);
-}
-
-// the same with a GATHERED residual (ABI 12): residual row of output row m = residual_gather[m * stride] (a global row index; rows
-// outside [0, residual_rows) add nothing) -- KPFCNN's decoder step split by linearity, (x W_x)[up[:, 0]] + skip W_skip (kpconv.py:283-286)
-extern "C" int ml3d_linear_bf16x3_gathered(const float* a, int64_t lda, int k1, const float* a2, int64_t lda2, int k2, int64_t rows,
-                                           const void* packed, const float* bias, const float* residual, int64_t ldr,
-                                           const int32_t* residual_gather, int64_t residual_gather_stride, int64_t residual_rows, int n,
-                                           int act, float slope, float* out, int64_t ldc, void* workspace, size_t workspace_bytes,
-                                           void* stream) {
-    if (rows < 0 || k1 <= 0 || k2 < 0 || n <= 0 || lda < k1 || (k2 > 0 && (!a2 || lda2 < k2)) || ldc < n || !a || !packed || !out ||
-        act < 0 || act > 2 || (residual && ldr < n) || (residual_gather && (!residual || residual_gather_stride < 1 || residual_rows < 0)))
-        return ML3D_E_INVALID;
-    Epilogue ep = {bias, residual, ldr, act, slope, 0, 0, 0, 0};
-    if (residual_gather) {      // global row indices: one "item" spanning every row
-        ep.res_gather = residual_gather; ep.rg_rows_per_item = (int64_t)1 << 62; ep.rg_src_rows_per_item = 0;
-        ep.rg_stride = residual_gather_stride; ep.rg_limit = residual_rows;
-    }
-    char* p = workspace ? (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255) : nullptr;
-    const size_t avail = workspace && workspace_bytes > 256 ? workspace_bytes - 256 : 0;
-    return gemm_rows_bf16x3(a, lda, k1, a2, lda2, k2, rows, packed, n, ep, out, ldc, p, avail, (hipStream_t)stream);
 }
 
 extern "C" int ml3d_nhwc_to_nchw(const float* in, int64_t in_pixel_stride, int channel_offset, int channels,

@@ -294,8 +294,7 @@ extern "C" int ml3d_conv3d_ndhwc_bf16x3(const float* in, int64_t batch, int d, i
     Conv3dA A;
     A.in = in; A.B = (int)batch; A.D = d; A.H = h; A.W = w; A.C = cin;
     if (!gemm_conv3d_bf16x3_ok(A)) return ML3D_E_UNSUPPORTED;
-    Epilogue ep = {bias, nullptr, 0, act, slope, 0, 0, 0, 0};
-    return gemm_conv3d_bf16x3(A, packed, cout, ep, out, out_voxel_stride, (hipStream_t)stream);
+    return gemm_conv3d_bf16x3(A, packed, cout, Epilogue::of(bias, act, slope), out, out_voxel_stride, (hipStream_t)stream);
 }
 
 extern "C" int ml3d_trilinear_devoxelize(const float* grid, int64_t ldg, int r, int c, const float* v, int64_t batch, int64_t n,

@@ -2870,7 +2870,7 @@ static int launch_linear_auto(const LinArgs& a, hipStream_t st) {
         const int K = a.c0 + (a.a1 ? a.c1 : 0);
         const size_t need = gemm_pack_bf16x3_bytes(K, a.cout);
         if (need > 0 && need <= a.pack_bytes && gemm_pack_bf16x3(a.wt, K, a.cout, a.pack_ws, st) == 0) {
-            Epilogue ep = {a.bias, nullptr, 0, a.act ? 1 : 0, a.slope, 0, 0, 0, 0, a.bias2};
+            const Epilogue ep = Epilogue::of(a.bias, a.act ? 1 : 0, a.slope).second_bias(a.bias2);
             const int rc = gemm_rows_bf16x3(a.a0, a.c0, a.c0, a.a1, a.c1, a.a1 ? a.c1 : 0, a.m_total, a.pack_ws, a.cout, ep, a.out,
                                             a.cout, nullptr, 0, st);
             if (rc != ML3D_E_UNSUPPORTED) return rc;
@@ -2882,7 +2882,7 @@ static int launch_linear_auto(const LinArgs& a, hipStream_t st) {
         A.gather = a.a1 ? a.gather : nullptr; A.gather_stride = 1; A.a_rows = a.a1_rows_per_item;
         A.a2 = a.a1; A.lda2 = a.c1; A.k2 = a.a1 ? a.c1 : 0;
         A.gather_on_a2 = 1; A.g_rows_per_item = a.rows_per_item; A.g_src_rows_per_item = a.a1_rows_per_item;
-        Epilogue ep = {a.bias, nullptr, 0, a.act ? 1 : 0, a.slope, 0, 0, 0, 0, a.bias2};
+        const Epilogue ep = Epilogue::of(a.bias, a.act ? 1 : 0, a.slope).second_bias(a.bias2);
         return gemm_rows(A, a.wt, a.m_total, a.cout, a.c0 + A.k2, ep, a.out, a.cout, nullptr, 0, st);
     }
     return launch_linear(a, st);
@@ -3272,13 +3272,13 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
             float* up = take(B * n[lev + 1] * skip_c);
             RowsA Au = {};
             Au.a = cur; Au.lda = cprev; Au.k1 = cprev;
-            Epilogue e0 = {};
             T.begin(1100 + i);
-            int rc = gemm_rows(Au, a.wt + (int64_t)skip_c * skip_c, B * n[lev + 1], skip_c, cprev, e0, up, skip_c, nullptr, 0, st);
+            int rc = gemm_rows(Au, a.wt + (int64_t)skip_c * skip_c, B * n[lev + 1], skip_c, cprev, Epilogue{}, up, skip_c, nullptr, 0, st);
             if (rc) return rc;
             RowsA As = {};
             As.a = a.a0; As.lda = skip_c; As.k1 = skip_c;
-            Epilogue e1 = {a.bias, up, skip_c, 1, 0.2f, 0, 0, 0, 0, nullptr, a.gather, n[lev], n[lev + 1], 0, n[lev + 1]};
+            // (the interpolation index is item-local: n[lev] rows per item here, n[lev + 1] coarse rows per item in `up`)
+            const Epilogue e1 = Epilogue::of(a.bias, 1, 0.2f).residual_rows(up, skip_c).gathered_residual(a.gather, 0, n[lev + 1], n[lev], n[lev + 1]);
             rc = gemm_rows(As, a.wt, a.m_total, skip_c, skip_c, e1, outp, skip_c, nullptr, 0, st);
             T.end(1100 + i);
             if (rc) return rc;

@@ -262,8 +262,7 @@ extern "C" int ml3d_sparse_conv_bf16x3(const float* in, int64_t ldi, int64_t in_
                                        int64_t ldc, void* stream) {
     if (act < 0 || act > 2 || !out || ldc < n || (residual && ldr < n)) return ML3D_E_INVALID;
     SparseConvA A = {in, ldi, in_rows, cp, rule, taps, a2, lda2, k2};
-    Epilogue ep = {bias, residual, ldr, act, slope, 0, 0, 0, 0};
-    return gemm_sparse_conv_bf16x3(A, m, packed, n, ep, out, ldc, (hipStream_t)stream);
+    return gemm_sparse_conv_bf16x3(A, m, packed, n, Epilogue::of(bias, act, slope).residual_rows(residual, ldr), out, ldc, (hipStream_t)stream);
 }
 
 extern "C" int ml3d_scn_bn_relu(const float* in, int64_t ldi, int64_t m, int c, const float* scale, const float* shift, float* out,

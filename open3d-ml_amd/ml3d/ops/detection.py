@@ -7,6 +7,7 @@ import torch
 from .. import _abi
 from . import _gates
 from ._gates import KnnResult, RadiusResult, VoxelizeResult, _splits, _splits_of_lengths
+from .gemm import pack_bf16x3, linear_bf16x3   # noqa: F401  (re-exported: their first callers were the BEV convolutions)
 
 
 def _stream():
@@ -49,24 +50,6 @@ def pillar_features(points, vox, in_channels, max_num_points, vx, vy, x_offset, 
     return canvas
 
 
-def pack_bf16x3(weights):
-    """Split a [K, N] float weight matrix (K % 32 == 0) once into the three bf16 planes `conv2d_nhwc(..., packed=)` multiplies
-    with on the bf16 matrix pipe (float32-equivalent result: include/ml3d_hip.h, ml3d_gemm_pack_bf16x3).  Returns a uint8
-    tensor, or None when the matrix is not eligible (the caller keeps the f32 kernel)."""
-    lib = _abi.get()
-    _need_gpu(weights)
-    K, N = int(weights.shape[0]), int(weights.shape[1])
-    nbytes = int(lib.ml3d_gemm_pack_bf16x3_bytes(K, N))
-    if nbytes == 0:
-        return None
-    w = weights.contiguous()
-    packed = torch.empty((nbytes,), dtype=torch.uint8, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = lib.ml3d_gemm_pack_bf16x3(w.data_ptr(), K, N, packed.data_ptr(), nbytes, _stream())
-    _abi.check(rc, "ml3d_gemm_pack_bf16x3")
-    return packed
-
-
 def conv2d_nhwc(x, weights, bias, kh, kw, stride, pad, act=2, slope=0.0, out=None, out_channel_offset=0, packed=None):
     """Conv2d + folded BN + activation on NHWC maps (SECOND, point_pillars.py:640-682).  `packed` = pack_bf16x3(weights) runs the
     same product on the bf16 matrix pipe (three-way split, float32-equivalent); `weights` still gives the shape."""
@@ -93,42 +76,6 @@ def conv2d_nhwc(x, weights, bias, kh, kw, stride, pad, act=2, slope=0.0, out=Non
                                   kh, kw, stride, pad, act, slope, cout, out.data_ptr() + 4 * out_channel_offset, ld,
                                   ws.data_ptr(), wsb, _stream())
     _abi.check(rc, "ml3d_conv2d_nhwc")
-    return out
-
-
-def linear_bf16x3(a, packed, n, bias=None, act=0, slope=0.0, a2=None, residual=None, residual_gather=None):
-    """act([a | a2] @ W + bias + residual) on the bf16 matrix pipe, `packed` = pack_bf16x3(W [K, n]) (float32-equivalent: pack_bf16x3).
-    ``residual_gather``: int32 [M, H] neighbour matrix whose first column selects the ROW of ``residual`` added to output row m
-    (rows >= residual.shape[0], the shadow index, add nothing) -- as ``ops.linear``.
-    Returns None when the problem is not eligible (block widths % 32, alignment): the caller keeps ops.linear."""
-    lib = _abi.get()
-    _need_gpu(a, bias, a2, residual, residual_gather)
-    for t in (a, a2, residual):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise RuntimeError("linear_bf16x3: float32 contiguous rows required")
-    m, k1 = a.shape
-    k2 = 0 if a2 is None else int(a2.shape[1])
-    if (k1 % 32) or (k2 % 32):
-        return None
-    out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    wsb = int(lib.ml3d_linear_bf16x3_workspace_bytes(m, int(n), k1 + k2))
-    ws = _ws(wsb, a.device)
-    with torch.cuda.device(a.device):
-        if residual_gather is not None:
-            if residual is None or residual_gather.dtype != torch.int32 or not residual_gather.is_contiguous() or residual_gather.shape[0] != m:
-                raise RuntimeError("linear_bf16x3: residual_gather must be a contiguous int32 [M, H] matrix next to a residual")
-            rg_stride = residual_gather.shape[1] if residual_gather.dim() == 2 else 1
-            rc = lib.ml3d_linear_bf16x3_gathered(a.data_ptr(), k1, k1, None if a2 is None else a2.data_ptr(), k2, k2, m, packed.data_ptr(),
-                                                 None if bias is None else bias.data_ptr(), residual.data_ptr(), int(n),
-                                                 residual_gather.data_ptr(), rg_stride, residual.shape[0], int(n), int(act), float(slope),
-                                                 out.data_ptr(), int(n), ws.data_ptr(), wsb, _stream())
-        else:
-            rc = lib.ml3d_linear_bf16x3(a.data_ptr(), k1, k1, None if a2 is None else a2.data_ptr(), k2, k2, m, packed.data_ptr(),
-                                        None if bias is None else bias.data_ptr(), None if residual is None else residual.data_ptr(),
-                                        int(n), int(n), int(act), float(slope), out.data_ptr(), int(n), ws.data_ptr(), wsb, _stream())
-    if rc == _abi.E_UNSUPPORTED:
-        return None
-    _abi.check(rc, "ml3d_linear_bf16x3")
     return out
 
 

@@ -7,6 +7,7 @@ import torch
 from .. import _abi
 from . import _gates
 from ._gates import KnnResult, RadiusResult, VoxelizeResult, _splits, _splits_of_lengths
+from .gemm import linear   # noqa: F401  (re-exported)
 
 
 def _stream():
@@ -86,49 +87,6 @@ def kpconv_deformable(q_pts, s_pts, neighb_inds, x, kernel_points, weights_kc_o,
                        influence=influence)
     return kpconv_rigid(q_pts, s_pts, neighb_inds, x, kernel_points, weights_kc_o, bias, extent, act=act, slope=slope,
                         influence=influence, offset_features=off)
-
-
-def linear(a, weights_t, bias=None, a2=None, gather=None, residual=None, act=0, slope=0.0, residual_gather=None):
-    """act([gather(a) | a2] @ weights_t + bias + residual) — UnaryBlock / decoder step (kpconv.py:1288-1293,
-    283-286).  gather: int32 [M, H] neighbour matrix whose FIRST column selects the row of ``a`` (closest_pool).
-    residual_gather: int32 [M, H] neighbour matrix whose first column selects the ROW OF ``residual`` added to output row m
-    (rows >= residual.shape[0], the shadow index, add nothing)."""
-    lib = _abi.get()
-    _need_gpu(a, weights_t, bias, a2, gather, residual)
-    dev = a.device
-    k1 = a.shape[1]
-    k2 = 0 if a2 is None else a2.shape[1]
-    n = weights_t.shape[1]
-    if weights_t.shape[0] != k1 + k2:
-        raise RuntimeError("linear: weight rows %d != input columns %d" % (weights_t.shape[0], k1 + k2))
-    if gather is not None:
-        if gather.dtype != torch.int32 or not gather.is_contiguous():
-            raise RuntimeError("linear: gather must be contiguous int32")
-        m, gstride = gather.shape[0], gather.shape[1] if gather.dim() == 2 else 1
-    else:
-        m, gstride = a.shape[0], 0
-    for t in (a, weights_t, bias, a2, residual):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-            raise RuntimeError("linear: float32 contiguous tensors required")
-    rg_stride = 0
-    if residual_gather is not None:
-        if residual is None or residual_gather.dtype != torch.int32 or not residual_gather.is_contiguous() or \
-                residual_gather.shape[0] != m:
-            raise RuntimeError("linear: residual_gather must be a contiguous int32 [M, H] matrix next to a residual")
-        rg_stride = residual_gather.shape[1] if residual_gather.dim() == 2 else 1
-    out = torch.empty((m, n), dtype=torch.float32, device=dev)
-    wsb = lib.ml3d_linear_workspace_bytes(m, n, k1 + k2)
-    ws = _ws(wsb, dev)
-    with torch.cuda.device(dev):
-        rc = lib.ml3d_linear(a.data_ptr(), k1, k1, None if gather is None else gather.data_ptr(), gstride, a.shape[0],
-                             None if a2 is None else a2.data_ptr(), k2, k2, weights_t.data_ptr(),
-                             None if bias is None else bias.data_ptr(),
-                             None if residual is None else residual.data_ptr(), n,
-                             None if residual_gather is None else residual_gather.data_ptr(), rg_stride,
-                             0 if residual is None else residual.shape[0], int(act), float(slope),
-                             out.data_ptr(), n, m, n, ws.data_ptr(), wsb, _stream())
-    _abi.check(rc, "ml3d_linear")
-    return out
 
 
 def gather_pool(x, inds, mode):

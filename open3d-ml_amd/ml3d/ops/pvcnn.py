@@ -7,7 +7,7 @@ import torch
 
 from .. import _abi
 from . import _gates
-from .detection import pack_bf16x3
+from .gemm import _rows, linear_rows_bf16x3, pack_bf16x3, pad32   # noqa: F401  (re-exported)
 
 
 def _stream():
@@ -16,14 +16,6 @@ def _stream():
 
 def _need_gpu(*tensors):
     return _gates._need_gpu(*tensors)
-
-
-def _rows(name, t, cols=None):
-    """A float32 [rows, cols] tensor or column slice (unit column stride) -> its row stride."""
-    if t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or (cols is not None and t.shape[1] != cols):
-        raise RuntimeError("%s: float32 rows with unit column stride%s required" %
-                           (name, "" if cols is None else " and %d columns" % cols))
-    return int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
 
 
 def pvcnn_voxel_coords(coords, resolutions):
@@ -78,7 +70,7 @@ def pack_conv3d_weights(weight, scale=None, shift=None, bias=None):
     if scale is not None:
         w = w * scale.view(-1, 1, 1, 1, 1)
         b = b * scale + shift
-    cp = (cin + 31) // 32 * 32
+    cp = pad32(cin)
     m = torch.zeros((27, cp, cout), dtype=torch.float64, device=w.device)
     m[:, :cin] = w.permute(2, 3, 4, 1, 0).reshape(27, cin, cout)
     return m.reshape(27 * cp, cout).float().contiguous(), b.float().contiguous(), cp
@@ -145,39 +137,5 @@ def segment_max_rows(x, batch):
     return out
 
 
-def linear_rows_bf16x3(a, packed, n, bias=None, act=0, slope=0.0, out=None, residual=None, residual_gather=None):
-    """``ops.linear_bf16x3`` for rows that are column slices: ``a`` [M, K] (K % 32 == 0) and ``out`` [M, n] may be slices of wider
-    buffers; ``residual`` [R, n] contiguous with ``residual_gather`` int32 [M] (row of ``residual`` added to output row m).  An
-    ineligible problem is an error here (the model has no other path)."""
-    _need_gpu(a, packed, bias, out, residual, residual_gather)
-    lib = _abi.get()
-    lda = _rows("linear_rows_bf16x3", a)
-    m, k = int(a.shape[0]), int(a.shape[1])
-    n = int(n)
-    if out is None:
-        out = torch.empty((m, n), dtype=torch.float32, device=a.device)
-    ldc = _rows("linear_rows_bf16x3", out, n)
-    if out.shape[0] != m or packed.numel() != int(lib.ml3d_gemm_pack_bf16x3_bytes(k, n)) or packed.numel() == 0:
-        raise RuntimeError("linear_rows_bf16x3: out / packed do not fit a [%d, %d] x [%d, %d] product" % (m, k, k, n))
-    wsb = int(lib.ml3d_linear_bf16x3_workspace_bytes(m, n, k))
-    ws = _gates._ws(wsb, a.device)
-    bp = None if bias is None else bias.data_ptr()
-    with torch.cuda.device(a.device):
-        if residual_gather is not None:
-            if residual is None or residual_gather.dtype != torch.int32 or not residual_gather.is_contiguous() or \
-                    residual_gather.numel() != m or not residual.is_contiguous() or residual.shape[1] != n:
-                raise RuntimeError("linear_rows_bf16x3: residual_gather must be contiguous int32 [M] next to a contiguous residual")
-            rc = lib.ml3d_linear_bf16x3_gathered(a.data_ptr(), lda, k, None, 0, 0, m, packed.data_ptr(), bp, residual.data_ptr(), n,
-                                                 residual_gather.data_ptr(), 1, int(residual.shape[0]), n, int(act), float(slope),
-                                                 out.data_ptr(), ldc, ws.data_ptr(), wsb, _stream())
-        else:
-            ldr = 0 if residual is None else _rows("linear_rows_bf16x3", residual, n)
-            rc = lib.ml3d_linear_bf16x3(a.data_ptr(), lda, k, None, 0, 0, m, packed.data_ptr(), bp,
-                                        None if residual is None else residual.data_ptr(), ldr, n, int(act), float(slope),
-                                        out.data_ptr(), ldc, ws.data_ptr(), wsb, _stream())
-    _abi.check(rc, "ml3d_linear_bf16x3")
-    return out
-
-
 __all__ = ["pvcnn_voxel_coords", "avg_voxelize", "pack_conv3d_weights", "conv3d_ndhwc", "trilinear_devoxelize", "segment_max_rows",
-           "linear_rows_bf16x3", "pack_bf16x3"]
+           "linear_rows_bf16x3", "pack_bf16x3", "pad32"]

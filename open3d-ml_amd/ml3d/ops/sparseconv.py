@@ -7,8 +7,7 @@ import torch
 
 from .. import _abi
 from . import _gates
-from .detection import pack_bf16x3
-from .pvcnn import _rows
+from .gemm import _rows, pack_bf16x3, pad32   # noqa: F401  (re-exported)
 
 
 def _stream():
@@ -17,10 +16,6 @@ def _stream():
 
 def _need_gpu(*tensors):
     return _gates._need_gpu(*tensors)
-
-
-def pad32(c):
-    return (int(c) + 31) // 32 * 32
 
 
 class ScnPyramid:

@@ -71,10 +71,6 @@ def _fold(weight, bias, bn=None, pad_to=None):
     return wt.float().contiguous(), b.float().contiguous()
 
 
-def _pad32(c):
-    return (c + 31) // 32 * 32
-
-
 # ---- the torch formulation of the ops (ML3D_PVCNN_OPS=torch) --------------------------------------------------------------------
 def _torch_avg_voxelize(feat, vox, batch, r, cg):
     n, c = feat.shape[0] // batch, feat.shape[1]
@@ -205,13 +201,13 @@ class PVCNN(nn.Module):
             for m in self.point_features:
                 if isinstance(m, PVConv):
                     vl = m.voxel_layers
-                    e = dict(kind="pvconv", r=m.resolution, cout=m.out_channels, cin_pad=_pad32(cin))
+                    e = dict(kind="pvconv", r=m.resolution, cout=m.out_channels, cin_pad=pv_ops.pad32(cin))
                     for tag, conv, bn in (("c1", vl[0], vl[1]), ("c2", vl[3], vl[4])):
                         s, t = _bn(bn)
                         w, b, _ = pv_ops.pack_conv3d_weights(conv.weight, s, t, conv.bias)
                         e[tag] = dict(w=w, b=b, packed=ops.pack_bf16x3(w))
                     pt = m.point_features.layers
-                    e["pt"] = self._pack_linear(pt[0].weight, pt[0].bias, pt[1], pad_to=_pad32(cin))
+                    e["pt"] = self._pack_linear(pt[0].weight, pt[0].bias, pt[1], pad_to=pv_ops.pad32(cin))
                     cin = m.out_channels
                 else:
                     e = dict(kind="mlp", cout=m.layers[0].out_channels)
@@ -261,7 +257,7 @@ class PVCNN(nn.Module):
         stats, vox = pv_ops.pvcnn_voxel_coords(coords, res)
         self.last_voxels = dict(stats=stats, vox={r: vox[r][1].view(B, N) for r in res})
 
-        x = torch.zeros((rows, _pad32(self.in_channels)), dtype=torch.float32, device=dev)
+        x = torch.zeros((rows, pv_ops.pad32(self.in_channels)), dtype=torch.float32, device=dev)
         x[:, :self.in_channels] = feat.transpose(1, 2).reshape(rows, self.in_channels)
         cat = torch.empty((rows, self.concat_channels), dtype=torch.float32, device=dev)
         off = 0

@@ -293,6 +293,93 @@ def test_bf16x3_linear_with_a_gathered_residual(m, mc, k, n, act):
     assert np.abs(out - ref).max() <= 2e-5
 
 
+def _epilogue_problem(k):
+    """The operands of the epilogue-mode tests: M = 130 rows (one full 64- / 128-row tile and a partial one), N = 36 columns (a partial
+    column tile, N % 4 == 0), weights scaled by 1 / sqrt(K) so that the product has unit variance at K = 64 and at K = 512."""
+    rng = np.random.default_rng(k)
+    m, n, mc = 130, 36, 40
+    a = rng.standard_normal((m, k)).astype(np.float32)
+    w = (rng.standard_normal((k, n)) / np.sqrt(k)).astype(np.float32)
+    b = rng.standard_normal(n).astype(np.float32)
+    r = rng.standard_normal((m, n)).astype(np.float32)
+    rc = rng.standard_normal((mc, n)).astype(np.float32)                # the coarse rows of the gathered residual
+    g = rng.integers(0, mc, (m, 3)).astype(np.int32)
+    g[77, 0] = mc                                                      # ONE row outside [0, mc): adds nothing
+    return a, w, b, r, rc, g
+
+
+def _act64(x, act, slope):
+    return {0: x, 1: np.where(x > 0, x, x * slope), 2: np.maximum(x, 0.0)}[act]
+
+
+@pytest.mark.parametrize("path", ["f32", "bf16x3", "f32-split", "bf16x3-split"])
+def test_every_epilogue_mode_at_every_store_site(path):
+    """plain, bias + leaky ReLU, bias + ReLU, residual, globally gathered residual (one index out of range) and the stride-2 pixel
+    shuffle through the three places that store a GEMM result: gemm_tile (64-row f32 kernel: ml3d_linear / ml3d_deconv2d_nhwc at
+    K = 64), tile2_epilogue (128-row bf16x3 kernel: ml3d_linear_bf16x3 / ml3d_deconv2d_nhwc_bf16x3 at K = 64) and gemm_reduce (K = 512:
+    both Linears cut K; of the deconvolutions only the f32 one takes a workspace).  Reference: the float64 product; bound: the 1e-5
+    of test_bf16x3_linear_matches_float64 (unit-variance sums plus unit-variance bias and residual stay below 8 in magnitude, where
+    a float32 ulp is 4.8e-7; 256 f32 accumulation steps of at most half an ulp each add up to about 1e-6 rms)."""
+    L = emu.lib()
+    bf3, split = path.startswith("bf16x3"), path.endswith("split")
+    k = 512 if split else 64
+    a, w, b, r, rcoarse, g = _epilogue_problem(k)
+    (m, n), mc, slope = r.shape, len(rcoarse), 0.2
+    ptr = lambda x: None if x is None else x.ctypes.data
+    wsb = int((L.ml3d_linear_bf16x3_workspace_bytes if bf3 else L.ml3d_linear_workspace_bytes)(m, n, k))
+    # (both *_workspace_bytes add 512 bytes of alignment slack to the partials: at least two slices of M * N floats when K is cut)
+    assert (wsb - 512 >= 2 * 4 * m * n) if split else (wsb == 512)
+    ws = np.zeros(wsb, np.uint8)
+    if bf3:
+        prc, packed = emu.pack_bf16x3(w)
+        assert prc == 0
+
+    def run(bias, act, res, gather):
+        out = np.full((m, n), np.nan, np.float32)
+        if bf3 and gather is not None:
+            rc = L.ml3d_linear_bf16x3_gathered(ptr(a), k, k, None, 0, 0, m, ptr(packed), ptr(bias), ptr(res), n, ptr(gather), gather.shape[1],
+                                               len(res), n, act, slope, ptr(out), n, ptr(ws), wsb, None)
+        elif bf3:
+            rc = L.ml3d_linear_bf16x3(ptr(a), k, k, None, 0, 0, m, ptr(packed), ptr(bias), ptr(res), n, n, act, slope, ptr(out), n, ptr(ws),
+                                      wsb, None)
+        else:
+            rc = L.ml3d_linear(ptr(a), k, k, None, 0, m, None, 0, 0, ptr(w), ptr(bias), ptr(res), n, ptr(gather),
+                               0 if gather is None else gather.shape[1], 0 if res is None else len(res), act, slope, ptr(out), n, m, n,
+                               ptr(ws), wsb, None)
+        assert rc == 0
+        return out
+
+    prod = a.astype(np.float64) @ w.astype(np.float64)
+    gathered = np.where((g[:, :1] >= 0) & (g[:, :1] < mc), rcoarse[np.clip(g[:, 0], 0, mc - 1)], 0.0)
+    for name, bias, act, res, gather, ref in [("plain", None, 0, None, None, prod),
+                                              ("bias + leaky", b, 1, None, None, prod + b),
+                                              ("bias + relu", b, 2, None, None, prod + b),
+                                              ("residual", b, 1, r, None, prod + b + r),
+                                              ("gathered residual", b, 1, rcoarse, g, prod + b + gathered)]:
+        err = np.abs(run(bias, act, res, gather) - _act64(ref, act, slope)).max()
+        print("%s, %s: max|d| = %.3g" % (path, name, err))
+        assert err <= 1e-5, (path, name, err)
+
+    # pixel shuffle, stride 2: the same A as a [1, 10, 13, K] map, N = 2 * 2 * 9 columns = (dy, dx, co), into a slice of a wider map
+    if path == "bf16x3-split":
+        return                                   # (ml3d_deconv2d_nhwc_bf16x3 takes no workspace: never cut along K)
+    h, wd, s, cout, ld, off = 10, 13, 2, 9, 16, 4
+    big = np.full((1, h * s, wd * s, ld), -1.0, np.float32)
+    if bf3:
+        rc = L.ml3d_deconv2d_nhwc_bf16x3(ptr(a), 1, h, wd, k, ptr(packed), ptr(b[:cout]), s, 2, 0.0, cout, ptr(big) + 4 * off, ld, None)
+    else:
+        dwsb = int(L.ml3d_conv2d_workspace_bytes(1, h, wd, k, n, 1, 1))
+        assert (dwsb - 512 >= 2 * 4 * m * n) if split else (dwsb == 512)
+        dws = np.zeros(dwsb, np.uint8)
+        rc = L.ml3d_deconv2d_nhwc(ptr(a), 1, h, wd, k, ptr(w), ptr(b[:cout]), s, 2, 0.0, cout, ptr(big) + 4 * off, ld, ptr(dws), dwsb, None)
+    assert rc == 0
+    ref = np.maximum(prod.reshape(h, wd, s, s, cout) + b[:cout], 0.0).transpose(0, 2, 1, 3, 4).reshape(1, h * s, wd * s, cout)
+    err = np.abs(big[..., off:off + cout] - ref).max()
+    print("%s, pixel shuffle: max|d| = %.3g" % (path, err))
+    assert err <= 1e-5, (path, "pixel shuffle", err)
+    assert (big[..., :off] == -1).all() and (big[..., off + cout:] == -1).all()
+
+
 def test_bf16x3_stride1_convolutions_through_both_kernels():
     """3 x 3 / stride 1 / pad 1 takes conv3x3s1_bf3 (the input window staged once per 16-channel chunk, border taps read a zero pixel);
     ML3D_CONV_WINDOW=0 (a test hook of the emulator build) sends the same problems through gemm_tile_bf3.  Shapes: image rows shorter

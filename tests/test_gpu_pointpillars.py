@@ -209,3 +209,66 @@ def test_both_convolution_paths_give_the_same_detections(monkeypatch):
     monkeypatch.setenv("ML3D_PP_CONV", "fp8")
     with pytest.raises(ValueError):
         _model(cfg, sd).packed_params(torch.device("cuda:0"))
+
+
+def _act64(x, act, slope):
+    return {0: x, 1: np.where(x > 0, x, x * slope), 2: np.maximum(x, 0.0)}[act]
+
+
+@pytest.mark.parametrize("path", ["f32", "bf16x3", "f32-split", "bf16x3-split"])
+def test_every_epilogue_mode_at_every_store_site(path):
+    """The GPU twin of tests/test_emulated_pillars.py::test_every_epilogue_mode_at_every_store_site (same shapes, data, float64
+    reference and 1e-5 bound): plain, bias + leaky ReLU, bias + ReLU, residual, globally gathered residual with one index out of
+    range and the stride-2 pixel shuffle through gemm_tile (f32, K = 64), tile2_epilogue (bf16x3, K = 64) and gemm_reduce (K = 512)."""
+    from ml3d import _abi, ops
+    lib = _abi.get()
+    bf3, split = path.startswith("bf16x3"), path.endswith("split")
+    k = 512 if split else 64
+    rng = np.random.default_rng(k)
+    m, n, mc, slope = 130, 36, 40, 0.2
+    a = rng.standard_normal((m, k)).astype(np.float32)
+    w = (rng.standard_normal((k, n)) / np.sqrt(k)).astype(np.float32)       # unit-variance sums at either K
+    b = rng.standard_normal(n).astype(np.float32)
+    r = rng.standard_normal((m, n)).astype(np.float32)
+    rcoarse = rng.standard_normal((mc, n)).astype(np.float32)
+    g = rng.integers(0, mc, (m, 3)).astype(np.int32)
+    g[77, 0] = mc                                                          # ONE row outside [0, mc): adds nothing
+    wsb = int((lib.ml3d_linear_bf16x3_workspace_bytes if bf3 else lib.ml3d_linear_workspace_bytes)(m, n, k))
+    assert (wsb - 512 >= 2 * 4 * m * n) if split else (wsb == 512)         # K = 512 really is cut: partials of >= 2 slices
+    dev = lambda x: None if x is None else torch.from_numpy(x).cuda()
+    da, dw = dev(a), dev(w)
+    packed = ops.pack_bf16x3(dw) if bf3 else None
+
+    def run(bias, act, res, gather):
+        if bf3:
+            out = ops.linear_bf16x3(da, packed, n, dev(bias), act=act, slope=slope, residual=dev(res), residual_gather=dev(gather))
+            assert out is not None
+        else:
+            out = ops.linear(da, dw, dev(bias), residual=dev(res), act=act, slope=slope, residual_gather=dev(gather))
+        return out.cpu().numpy()
+
+    prod = a.astype(np.float64) @ w.astype(np.float64)
+    gathered = np.where((g[:, :1] >= 0) & (g[:, :1] < mc), rcoarse[np.clip(g[:, 0], 0, mc - 1)], 0.0)
+    for name, bias, act, res, gather, ref in [("plain", None, 0, None, None, prod),
+                                              ("bias + leaky", b, 1, None, None, prod + b),
+                                              ("bias + relu", b, 2, None, None, prod + b),
+                                              ("residual", b, 1, r, None, prod + b + r),
+                                              ("gathered residual", b, 1, rcoarse, g, prod + b + gathered)]:
+        err = np.abs(run(bias, act, res, gather) - _act64(ref, act, slope)).max()
+        print("%s, %s: max|d| = %.3g" % (path, name, err))
+        assert err <= 1e-5, (path, name, err)
+
+    if path == "bf16x3-split":
+        return                                   # (the bf16x3 deconvolution takes no workspace: never cut along K)
+    h, wd, s, cout, ld, off = 10, 13, 2, 9, 16, 4
+    if not bf3:
+        dwsb = int(lib.ml3d_conv2d_workspace_bytes(1, h, wd, k, n, 1, 1))
+        assert (dwsb - 512 >= 2 * 4 * m * n) if split else (dwsb == 512)
+    big = torch.full((1, h * s, wd * s, ld), -1.0, dtype=torch.float32, device="cuda:0")
+    ops.deconv2d_nhwc(da.view(1, h, wd, k), dw, dev(b[:cout].copy()), s, cout, act=2, out=big, out_channel_offset=off, packed=packed)
+    big = big.cpu().numpy()
+    ref = np.maximum(prod.reshape(h, wd, s, s, cout) + b[:cout], 0.0).transpose(0, 2, 1, 3, 4).reshape(1, h * s, wd * s, cout)
+    err = np.abs(big[..., off:off + cout] - ref).max()
+    print("%s, pixel shuffle: max|d| = %.3g" % (path, err))
+    assert err <= 1e-5, (path, "pixel shuffle", err)
+    assert (big[..., :off] == -1).all() and (big[..., off + cout:] == -1).all()
