@@ -20,7 +20,8 @@
  *    point is to do a batch build's size read-backs inside the call;
  *  - HIP graph capture (hipStreamBeginCapture on `stream`): the RandLA path
  *    (ml3d_randla_knn_pyramid*, ml3d_randla_forward*, ml3d_nearest_to_center_dev,
- *    ml3d_patch_crop / _recenter, ml3d_vote_update) contains kernel nodes only
+ *    ml3d_patch_crop / _recenter, ml3d_possibility_argmin, ml3d_patch_batch,
+ *    ml3d_vote_update) contains kernel nodes only
  *    and replays correctly (tests/test_gpu_api.py).  Other entry points clear
  *    buffers with hipMemsetAsync, and on ROCm 7.2 a captured graph's memset
  *    node was observed NOT to clear its target on later replays:
@@ -652,6 +653,48 @@ int ml3d_patch_crop(const float* points, int64_t n_points, const int32_t* cand, 
 int ml3d_patch_recenter(float* pts, int64_t k, int dims_mask, const float* extra, int n_extra,
                         float feat_bias, float feat_scale, float* out_features,
                         void* scratch, size_t scratch_bytes, void* stream);
+
+/* ---- the patch loop of SEVERAL clouds in lock step (multi-cloud patch loop) -------------------- */
+/* The patches of a cloud depend only on that cloud's possibilities and its own shuffles, never on  */
+/* a logit, so C clouds can each give one patch per ROUND and still produce exactly the sequence    */
+/* each would produce alone: the forward gets a real batch, the C dependent chains of the entries   */
+/* above (an 8-pass sort of one cloud, one workgroup adding num_points floats in order) run as one. */
+/* The clouds in flight lie back to back: points [N, 3], possibility [N] (float64), extra [N, c];   */
+/* cloud_row_splits_host: HOST int64 [n_clouds + 1], monotone, [0] == 0, n_clouds <= 256 (slot s =   */
+/* rows [splits[s], splits[s + 1])); active_host: HOST int32 [n_active], the slots this call serves, */
+/* strictly ascending (a retired slot is simply left out; its rows and outputs are not touched).    */
+/* Both host arrays are read during the call only.  Kernel nodes only, nothing synchronises.        */
+/* ml3d_possibility_argmin: out_index[s] = the FIRST index (cloud-local) of the minimum of slot s's  */
+/*   possibilities (np.argmin / torch.argmin order), out_min[s] = that minimum (the host's "cloud    */
+/*   finished" test: one read-back per round); both [n_clouds], written for active slots only.      */
+/*   Deterministic: per-tile partial results (tiles never cross a cloud), then one wave per cloud.  */
+/*   Workspace: n_points = the points of the active clouds (any upper bound, e.g. N, will do).      */
+/* ml3d_patch_batch: one round.  For the a-th active slot s, with centre = points[splits[s] +        */
+/*   center_index[s]] (center_index: DEVICE int32 [n_clouds], e.g. out_index above) and perm row a  */
+/*   (DEVICE int32 [n_active, k], the host's shuffle of 0..k-1 for that cloud), it writes            */
+/*   out_pts[a] [k, 3], out_features[a] [k, 3 + n_extra], out_sel[a] [k] (cloud-local indices) and  */
+/*   out_row[a] [k] (= out_sel + splits[s]: rows of the concatenated arrays, for the labels gather  */
+/*   and ml3d_vote_update on a concatenated accumulator) and bumps `possibility` in place -- bit for */
+/*   bit what ml3d_nearest_to_center_dev(k) -> ml3d_patch_crop -> ml3d_patch_recenter give on that   */
+/*   cloud alone (same float64 order key, ties by ascending index; same float32 distances, bump,    */
+/*   per-cloud maximum, SEQUENTIAL column sums, features): the arithmetic is shared in the source.   */
+/*   k <= every active cloud's size (ML3D_E_INVALID otherwise).  extra: [N, n_extra] or NULL / 0.    */
+/*   Method: ONE 64-bit sort of all active points by distance to their own cloud's centre, one      */
+/*   stable pass keyed by cloud, the first k of every segment; the n_active sequential means run    */
+/*   side by side, one workgroup each.                                                              */
+size_t ml3d_possibility_argmin_workspace_bytes(int64_t n_points, int64_t n_clouds);
+
+int ml3d_possibility_argmin(const double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                            const int32_t* active_host, int64_t n_active, int32_t* out_index, double* out_min,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+size_t ml3d_patch_batch_workspace_bytes(int64_t n_points, int64_t n_active, int64_t k);
+
+int ml3d_patch_batch(const float* points, double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                     const int32_t* active_host, int64_t n_active, const int32_t* center_index, const int32_t* perm,
+                     int64_t k, int dims_mask, const float* extra, int n_extra, float feat_bias, float feat_scale,
+                     float* out_pts, float* out_features, int32_t* out_sel, int32_t* out_row,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- RandLA-Net random_sample as a differentiable op (training side, SURVEY.md §8 f4, ABI 5) ------------------ */
 /* ml3d_randla_gather_max: out[b, i, c] = max_k features[b, pool_idx[b, i, k], c], i < n_out (randlanet.py:300-327;   */

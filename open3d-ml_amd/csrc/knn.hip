@@ -645,6 +645,7 @@ extern "C" int ml3d_randla_knn_pyramid_ordered(const float* points, int64_t batc
 // ---------------------------------------------------------------------------------------------------
 #include <hip/hip_fp16.h>
 
+#include "patchloop.h"
 #include "sort.h"
 
 namespace ml3d {
@@ -659,8 +660,7 @@ __global__ void center_keys(const float* __restrict__ pts, int64_t n, double cx,
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (cdev) { cx = (double)cdev[0]; cy = (double)cdev[1]; cz = (double)cdev[2]; }
-    const double dx = (double)pts[3 * i] - cx, dy = (double)pts[3 * i + 1] - cy, dz = (double)pts[3 * i + 2] - cz;
-    const double d2 = (dx * dx + dy * dy) + dz * dz;      // -ffp-contract=off: three products, two sums, no FMA
+    const double d2 = center_d2_f64(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], cx, cy, cz);      // (patchloop.h)
     keys[i] = (u64)__double_as_longlong(d2);
     vals[i] = (uint32_t)i;
 }
@@ -831,9 +831,7 @@ patch_gather(const float* __restrict__ pts, const int32_t* __restrict__ cand, co
         const float x = pts[3 * (int64_t)i], y = pts[3 * (int64_t)i + 1], z = pts[3 * (int64_t)i + 2];
         out_pts[3 * j] = x; out_pts[3 * j + 1] = y; out_pts[3 * j + 2] = z;
         out_sel[j] = i;
-        // np.sum(np.square((pc - center).astype(np.float32)), axis=1): three float32 squares added left to right
-        const float dx = __fsub_rn(x, center[0]), dy = __fsub_rn(y, center[1]), dz = __fsub_rn(z, center[2]);
-        d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+        d = patch_d2_f32(x, y, z, center);      // (patchloop.h: numpy's float32 squares, added left to right)
         d2[j] = d;
     }
     // max of non-negative floats == max of their bit patterns
@@ -849,71 +847,13 @@ patch_bump(const int32_t* __restrict__ sel, const float* __restrict__ d2, const 
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= k) return;
     const float mx = __uint_as_float(*d2max_bits);
-    const float t = __fsub_rn(1.0f, __fdiv_rn(d2[j], mx));          // float32: 1 - dists / np.max(dists)
-    possibility[sel[j]] += (double)__fmul_rn(t, t);                 // float64 += float32 square
+    possibility[sel[j]] += (double)patch_bump_f32(d2[j], mx);       // float64 += float32 (1 - dists / np.max(dists))^2
 }
 
-// one workgroup, two LDS stages of 2 560 rows (column-major): waves 1..3 transpose stage i + 1 in while threads 0..2 of wave 0 add
-// their column of stage i IN ROW ORDER -- the chain is the 45 056 dependent additions, so everything else is kept off it: the
-// next stage's global reads and LDS writes run beside it, 16-byte LDS reads, eight of them (32 values) in flight under the 32
-// adds of the previous block, two register blocks in ping-pong (no copies)
+// one workgroup adds the three columns in row order (patchloop.h: the body is shared with the batched round of patchloop.hip)
 __global__ void __launch_bounds__(256)
 patch_mean_seq(const float* __restrict__ pts, int64_t k, float* __restrict__ mean_out) {
-    constexpr int ROWS = 2560;            // 30 KB of LDS per stage
-    __shared__ __attribute__((aligned(16))) float buf[2][3 * ROWS];
-    auto fill = [&](int64_t base, float* dst, int first, int step) {
-        if (base >= k) return;
-        const int rows = (int)min<int64_t>(ROWS, k - base);
-        for (int e = first; e < rows * 3; e += step) {
-            const int r = e / 3, c = e - 3 * r;
-            dst[c * ROWS + r] = pts[3 * base + e];
-        }
-    };
-    fill(0, buf[0], threadIdx.x, 256);
-    __syncthreads();
-    float s = 0.f;
-    int stage = 0;
-    for (int64_t base = 0; base < k; base += ROWS, stage ^= 1) {
-        const int rows = (int)min<int64_t>(ROWS, k - base);
-        if (threadIdx.x >= 64) {
-            fill(base + ROWS, buf[stage ^ 1], threadIdx.x - 64, 192);
-        } else if (threadIdx.x < 3) {
-            const float* col = buf[stage] + threadIdx.x * ROWS;
-            const float4* col4 = reinterpret_cast<const float4*>(col);
-            int r = 0;
-            // blocks of 256 rows as STRAIGHT-LINE code, eight groups of 32 rows: the 16-byte LDS reads of group g + 1 are issued,
-            // then the 32 dependent adds of group g run under them -- two register sets in ping-pong with nothing carried
-            // around a loop (the rolled two-block loop this replaces paid a v_mov per add for half of the rows, the phi copies
-            // of its prefetch registers); only a block's first group is exposed, once per 256 adds.  The scheduling barriers keep
-            // the compiler from hoisting all 64 reads to the top (it did: the first add then waited for 46 of them).
-            for (; r + 256 <= rows; r += 256) {
-                const float4* c4 = col4 + r / 4;
-                float4 a[8], b[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) a[i] = c4[i];
-#pragma unroll
-                for (int g = 0; g < 8; g += 2) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) b[i] = c4[8 * (g + 1) + i];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) { s = __fadd_rn(s, a[i].x); s = __fadd_rn(s, a[i].y); s = __fadd_rn(s, a[i].z); s = __fadd_rn(s, a[i].w); }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (g + 2 < 8) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) a[i] = c4[8 * (g + 2) + i];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) { s = __fadd_rn(s, b[i].x); s = __fadd_rn(s, b[i].y); s = __fadd_rn(s, b[i].z); s = __fadd_rn(s, b[i].w); }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            for (; r < rows; ++r) s = __fadd_rn(s, col[r]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) mean_out[threadIdx.x] = __fdiv_rn(s, (float)k);
+    patch_mean_seq_body(pts, k, mean_out);
 }
 
 __global__ void __launch_bounds__(256)
@@ -929,7 +869,7 @@ patch_apply(float* __restrict__ pts, int64_t k, int dims_mask, const float* __re
         if (feats) feats[j * C + d] = v;
     }
     if (feats)
-        for (int c = 0; c < n_extra; ++c) feats[j * C + 3 + c] = __fdiv_rn(__fsub_rn(extra[j * n_extra + c], bias), scale);
+        for (int c = 0; c < n_extra; ++c) feats[j * C + 3 + c] = patch_feat_f32(extra[j * n_extra + c], bias, scale);
 }
 
 }  // namespace ml3d

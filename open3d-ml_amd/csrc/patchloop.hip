@@ -1,0 +1,326 @@
+// patchloop.hip — the spatially regular patch loop for SEVERAL clouds in lock step (gfx950; ml3d_hip.h, "multi-cloud patch loop").
+//
+// The single-cloud loop (knn.hip: ml3d_nearest_to_center_dev -> ml3d_patch_crop -> ml3d_patch_recenter) is a chain of small,
+// dependent launches per patch -- an 8-pass radix sort of one cloud, one workgroup adding 45 056 floats in order -- and C clouds
+// make C such chains.  The patches of a cloud depend on nothing but that cloud's possibilities and its own shuffles, so the
+// clouds can advance together: one round here cuts one patch out of EVERY active cloud, bit for bit the patch the single-cloud
+// entries would cut (the arithmetic is shared through patchloop.h), with the launches of one chain:
+//   ml3d_possibility_argmin   per-tile partial (minimum, first index) -> one wave per cloud combines them   [2 launches]
+//   ml3d_patch_batch          keys of all active points -> ONE 64-bit sort by distance -> one stable 8-bit pass by cloud ->
+//                             crop + distances + maxima -> possibility bump -> the A sequential means SIDE BY SIDE (one workgroup
+//                             per cloud) -> recentre + features
+// The clouds lie back to back in device arrays; their boundaries (cloud_row_splits) and the list of active slots are HOST arrays,
+// read during the call and carried to the kernels by value (PbItems): no upload, no allocation, kernel nodes only.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "grid.h"
+#include "ml3d_hip.h"
+#include "patchloop.h"
+#include "sort.h"
+
+namespace ml3d {
+
+constexpr int PB_ITEMS = 64;          // active clouds one launch serves (a call with more launches its item kernels in chunks)
+constexpr int PB_MAX_CLOUDS = 256;    // the cloud of a point is an 8-bit sort key
+constexpr int PB_TILE = 2048;         // possibilities per argmin tile (256 threads x 8)
+
+// the active clouds of one launch, by value in the kernel arguments (1.3 KB)
+struct PbItems {
+    int slot[PB_ITEMS];        // cloud slot (index into cloud_row_splits / the per-cloud outputs)
+    int start[PB_ITEMS];       // first row of the cloud in the concatenated arrays
+    int len[PB_ITEMS];         // its number of points
+    int cstart[PB_ITEMS];      // first position of the cloud among the points of the ACTIVE clouds (the sort's index space)
+    int tile0[PB_ITEMS];       // first argmin tile of the cloud
+    int first;                 // ordinal of item 0 of this launch among the active clouds of the call
+};
+
+// (value, index) pairs order like np.argmin: the smaller value, on equal values the smaller index
+__device__ __forceinline__ void argmin_take(double& v, int& i, double ov, int oi) {
+    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+__device__ __forceinline__ void argmin_wave(double& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        argmin_take(v, i, ov, oi);
+    }
+}
+constexpr int ARGMIN_NONE = 0x7fffffff;
+
+// stage one: tile blockIdx.x of item blockIdx.y (tiles never cross a cloud boundary) -> its minimum and the first index holding it
+__global__ void __launch_bounds__(256)
+pb_argmin_tiles(const double* __restrict__ poss, PbItems it, double* __restrict__ part_v, int* __restrict__ part_i) {
+    __shared__ double sv[4];
+    __shared__ int si[4];
+    const int a = blockIdx.y;
+    const int len = it.len[a];
+    const int t0 = (int)blockIdx.x * PB_TILE;
+    if (t0 >= len) return;                                   // (uniform over the workgroup)
+    const int end = min(len, t0 + PB_TILE);
+    const double* p = poss + it.start[a];
+    double v = __longlong_as_double(0x7ff0000000000000ll);   // +inf
+    int idx = ARGMIN_NONE;
+    for (int i = t0 + (int)threadIdx.x; i < end; i += 256) {
+        const double x = p[i];
+        if (x < v || idx == ARGMIN_NONE) { v = x; idx = i; }  // ascending i per thread: '<' keeps the first
+    }
+    argmin_wave(v, idx);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = v; si[threadIdx.x >> 6] = idx; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) argmin_take(v, idx, sv[w], si[w]);
+        part_v[it.tile0[a] + blockIdx.x] = v;
+        part_i[it.tile0[a] + blockIdx.x] = idx;
+    }
+}
+
+// stage two: one wave per item combines its tiles' partial results
+__global__ void __launch_bounds__(64)
+pb_argmin_final(const double* __restrict__ part_v, const int* __restrict__ part_i, PbItems it, int32_t* __restrict__ out_index,
+                double* __restrict__ out_min) {
+    const int a = blockIdx.x;
+    const int tiles = (it.len[a] + PB_TILE - 1) / PB_TILE;
+    double v = __longlong_as_double(0x7ff0000000000000ll);
+    int idx = ARGMIN_NONE;
+    for (int t = threadIdx.x; t < tiles; t += 64) argmin_take(v, idx, part_v[it.tile0[a] + t], part_i[it.tile0[a] + t]);
+    argmin_wave(v, idx);
+    if (threadIdx.x == 0) { out_index[it.slot[a]] = idx; out_min[it.slot[a]] = v; }
+}
+
+// the centre of item a: the point its argmin picked (an index outside the cloud is clamped, never followed)
+__device__ __forceinline__ const float* pb_center(const float* __restrict__ pts, const PbItems& it, int a,
+                                                  const int32_t* __restrict__ center_index) {
+    int c = center_index[it.slot[a]];
+    c = c < 0 ? 0 : (c >= it.len[a] ? it.len[a] - 1 : c);
+    return pts + 3 * ((int64_t)it.start[a] + c);
+}
+
+// sort keys of the points of the active clouds: position cstart[a] + i <- (float64 reduced distance to the cloud's own centre, i)
+__global__ void __launch_bounds__(256)
+pb_keys(const float* __restrict__ pts, PbItems it, const int32_t* __restrict__ center_index, u64* __restrict__ keys,
+        uint32_t* __restrict__ vals, uint32_t* __restrict__ item_of) {
+    const int a = blockIdx.y;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= it.len[a]) return;
+    const float* c = pb_center(pts, it, a, center_index);
+    const float* p = pts + 3 * ((int64_t)it.start[a] + i);
+    const double d2 = center_d2_f64(p[0], p[1], p[2], (double)c[0], (double)c[1], (double)c[2]);
+    const int64_t pos = (int64_t)it.cstart[a] + i;
+    keys[pos] = (u64)__double_as_longlong(d2);
+    vals[pos] = (uint32_t)pos;                                // ascending within a cloud: the stable sort breaks ties by index
+    item_of[pos] = (uint32_t)(it.first + a);
+}
+
+// the second sort's key: the cloud (ordinal among the active ones) of the point now at sorted position i
+__global__ void __launch_bounds__(256)
+pb_item_keys(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ item_of, int64_t m, u64* __restrict__ keys) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) keys[i] = (u64)item_of[vals[i]];
+}
+
+// ml3d_patch_crop's gather for item blockIdx.y: sorted[cstart .. cstart + len) are the cloud's points by ascending distance
+__global__ void __launch_bounds__(256)
+pb_gather(const float* __restrict__ pts, const uint32_t* __restrict__ sorted, PbItems it, const int32_t* __restrict__ center_index,
+          const int32_t* __restrict__ perm, int64_t k, float* __restrict__ out_pts, int32_t* __restrict__ out_sel,
+          int32_t* __restrict__ out_row, float* __restrict__ d2, unsigned* __restrict__ d2max_bits) {
+    const int a = blockIdx.y;
+    const int64_t item = it.first + a;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float d = 0.f;
+    if (j < k) {
+        int32_t q = perm[item * k + j];
+        q = q < 0 ? 0 : (q >= k ? (int32_t)(k - 1) : q);       // (a shuffle of 0..k-1; anything else is clamped, never followed)
+        const int32_t i = (int32_t)(sorted[(int64_t)it.cstart[a] + q] - (uint32_t)it.cstart[a]);
+        const int64_t row = (int64_t)it.start[a] + i;
+        const float x = pts[3 * row], y = pts[3 * row + 1], z = pts[3 * row + 2];
+        const int64_t o = item * k + j;
+        out_pts[3 * o] = x; out_pts[3 * o + 1] = y; out_pts[3 * o + 2] = z;
+        out_sel[o] = i;
+        out_row[o] = (int32_t)row;
+        d = patch_d2_f32(x, y, z, pb_center(pts, it, a, center_index));
+        d2[o] = d;
+    }
+    // max of non-negative floats == max of their bit patterns
+    unsigned b = __float_as_uint(d);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(d2max_bits + item, b);
+}
+
+__global__ void __launch_bounds__(256)
+pb_bump(const int32_t* __restrict__ out_row, const float* __restrict__ d2, const unsigned* __restrict__ d2max_bits, int64_t k,
+        double* __restrict__ possibility) {
+    const int64_t item = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= k) return;
+    const int64_t o = item * k + j;
+    possibility[out_row[o]] += (double)patch_bump_f32(d2[o], __uint_as_float(d2max_bits[item]));
+}
+
+// the A sequential column sums side by side: one workgroup per item
+__global__ void __launch_bounds__(256)
+pb_mean_seq(const float* __restrict__ pts, int64_t k, float* __restrict__ mean) {
+    patch_mean_seq_body(pts + 3 * k * (int64_t)blockIdx.x, k, mean + 4 * (int64_t)blockIdx.x);
+}
+
+__global__ void __launch_bounds__(256)
+pb_apply(float* __restrict__ pts, int64_t k, int dims_mask, const float* __restrict__ mean, const int32_t* __restrict__ out_row,
+         const float* __restrict__ extra, int n_extra, float bias, float scale, float* __restrict__ feats) {
+    const int64_t item = blockIdx.y;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= k) return;
+    const int64_t o = item * k + j;
+    const int C = 3 + n_extra;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        float v = pts[3 * o + d];
+        if (dims_mask & (1 << d)) { v = __fsub_rn(v, mean[4 * item + d]); pts[3 * o + d] = v; }
+        feats[o * C + d] = v;
+    }
+    const float* ex = n_extra ? extra + (int64_t)out_row[o] * n_extra : nullptr;
+    for (int c = 0; c < n_extra; ++c) feats[o * C + 3 + c] = patch_feat_f32(ex[c], bias, scale);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+static inline size_t pb_al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// the active clouds of a call, checked: splits monotone from 0, slots strictly ascending (so distinct) and inside [0, n_clouds),
+// every active cloud with at least min_len points.  Returns the points of the active clouds, < 0 on a bad argument.
+static int64_t pb_check(const int64_t* splits, int64_t n_clouds, const int32_t* active, int64_t n_active, int64_t min_len) {
+    if (!splits || !active || n_clouds < 1 || n_clouds > PB_MAX_CLOUDS || n_active < 1 || n_active > n_clouds) return -1;
+    if (splits[0] != 0) return -1;
+    for (int64_t c = 0; c < n_clouds; ++c)
+        if (splits[c + 1] < splits[c]) return -1;
+    if (splits[n_clouds] > 0x7ffffff0ll) return -1;
+    int64_t m = 0;
+    for (int64_t a = 0; a < n_active; ++a) {
+        const int64_t s = active[a];
+        if (s < 0 || s >= n_clouds || (a > 0 && s <= active[a - 1])) return -1;
+        const int64_t len = splits[s + 1] - splits[s];
+        if (len < 1 || len < min_len) return -1;
+        m += len;
+    }
+    return m;
+}
+
+// items [first, first + count) of the call as a kernel argument; *longest = the longest of them
+static PbItems pb_items(const int64_t* splits, const int32_t* active, int64_t first, int count, int* longest) {
+    PbItems it;
+    int64_t cstart = 0, tile0 = 0;
+    for (int64_t a = 0; a < first; ++a) {
+        const int64_t len = splits[active[a] + 1] - splits[active[a]];
+        cstart += len;
+        tile0 += (len + PB_TILE - 1) / PB_TILE;
+    }
+    *longest = 0;
+    for (int a = 0; a < PB_ITEMS; ++a) {
+        const bool live = a < count;
+        const int64_t s = live ? active[first + a] : 0;
+        const int64_t len = live ? splits[s + 1] - splits[s] : 0;
+        it.slot[a] = (int)s; it.start[a] = live ? (int)splits[s] : 0; it.len[a] = (int)len;
+        it.cstart[a] = (int)cstart; it.tile0[a] = (int)tile0;
+        cstart += len;
+        tile0 += (len + PB_TILE - 1) / PB_TILE;
+        if (len > *longest) *longest = (int)len;
+    }
+    it.first = (int)first;
+    return it;
+}
+
+}  // namespace ml3d
+
+using namespace ml3d;
+
+extern "C" size_t ml3d_possibility_argmin_workspace_bytes(int64_t n_points, int64_t n_clouds) {
+    if (n_points < 0 || n_clouds < 0) return 0;
+    const size_t tiles = (size_t)(n_points / PB_TILE + n_clouds + 1);
+    return pb_al(sizeof(double) * tiles) + pb_al(sizeof(int) * tiles) + 512;
+}
+
+extern "C" int ml3d_possibility_argmin(const double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                                       const int32_t* active_host, int64_t n_active, int32_t* out_index, double* out_min,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    const int64_t m = pb_check(cloud_row_splits_host, n_clouds, active_host, n_active, 1);
+    if (m < 0 || !possibility || !out_index || !out_min || !workspace) return ML3D_E_INVALID;
+    if (workspace_bytes < ml3d_possibility_argmin_workspace_bytes(m, n_active)) return ML3D_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t tiles = (size_t)(m / PB_TILE + n_active + 1);
+    char* p = ws_align(workspace);
+    double* part_v = (double*)p;  p += pb_al(sizeof(double) * tiles);
+    int* part_i = (int*)p;
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        int longest;
+        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+        hipLaunchKernelGGL(pb_argmin_tiles, dim3((unsigned)((longest + PB_TILE - 1) / PB_TILE), (unsigned)count), dim3(256), 0, st,
+                           possibility, it, part_v, part_i);
+        hipLaunchKernelGGL(pb_argmin_final, dim3((unsigned)count), dim3(64), 0, st, part_v, part_i, it, out_index, out_min);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" size_t ml3d_patch_batch_workspace_bytes(int64_t n_points, int64_t n_active, int64_t k) {
+    if (n_points < 0 || n_active < 0 || k < 0) return 0;
+    const int64_t m = n_points > 0 ? n_points : 1;
+    return pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active) +      // per item: the maximum-distance word, the three means
+           pb_al(sizeof(float) * (size_t)n_active * (size_t)k) + pb_al(sizeof(u64) * (size_t)m) + 2 * pb_al(sizeof(uint32_t) * (size_t)m) +
+           sort_ws_bytes(m) + 512;
+}
+
+extern "C" int ml3d_patch_batch(const float* points, double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                                const int32_t* active_host, int64_t n_active, const int32_t* center_index, const int32_t* perm,
+                                int64_t k, int dims_mask, const float* extra, int n_extra, float feat_bias, float feat_scale,
+                                float* out_pts, float* out_features, int32_t* out_sel, int32_t* out_row, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    if (k < 1 || n_extra < 0 || (n_extra > 0 && !extra) || (dims_mask & ~7)) return ML3D_E_INVALID;
+    const int64_t m = pb_check(cloud_row_splits_host, n_clouds, active_host, n_active, k);
+    if (m < 0 || n_active * k > 0x7ffffff0ll) return ML3D_E_INVALID;
+    if (!points || !possibility || !center_index || !perm || !out_pts || !out_features || !out_sel || !out_row || !workspace)
+        return ML3D_E_INVALID;
+    if (workspace_bytes < ml3d_patch_batch_workspace_bytes(m, n_active, k)) return ML3D_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* p = ws_align(workspace);
+    unsigned* mx = (unsigned*)p;      p += pb_al(4 * (size_t)n_active);       // [n_active]     bits of the largest float32 distance
+    float* mean = (float*)p;          p += pb_al(16 * (size_t)n_active);      // [n_active][4]  column means
+    float* d2 = (float*)p;            p += pb_al(sizeof(float) * (size_t)n_active * (size_t)k);
+    u64* keys = (u64*)p;              p += pb_al(sizeof(u64) * (size_t)m);
+    uint32_t* vals = (uint32_t*)p;    p += pb_al(sizeof(uint32_t) * (size_t)m);
+    uint32_t* item_of = (uint32_t*)p; p += pb_al(sizeof(uint32_t) * (size_t)m);
+    SortWs sw;
+    if (!sort_ws_carve(p, sort_ws_bytes(m), m, &sw)) return ML3D_E_WORKSPACE;
+    zero_async(mx, pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active), st);      // (a fill kernel, not hipMemsetAsync: grid.h)
+    const unsigned kblocks = (unsigned)((k + 255) / 256);
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        int longest;
+        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+        hipLaunchKernelGGL(pb_keys, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, points, it, center_index,
+                           keys, vals, item_of);
+    }
+    if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
+    // all points of the active clouds by distance to their own cloud's centre, then ONE stable pass by cloud: every cloud's
+    // points end up contiguous (in the order of the active list) and ascending in (distance, index)
+    if (sort_pairs_u64(keys, vals, m, 64, sw, st)) return ML3D_E_LAUNCH;
+    const uint32_t* sorted = vals;
+    if (n_active > 1) {
+        int bits = 1;
+        while ((1ll << bits) < n_active) ++bits;
+        hipLaunchKernelGGL(pb_item_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, vals, item_of, m, keys);
+        if (sort_pairs_u64(keys, vals, m, bits, sw, st, true)) return ML3D_E_LAUNCH;
+        if (sort_result_in_alt(m, bits)) sorted = sw.vals_alt;
+    }
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        int longest;
+        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+        hipLaunchKernelGGL(pb_gather, dim3(kblocks, (unsigned)count), dim3(256), 0, st, points, sorted, it, center_index, perm, k, out_pts,
+                           out_sel, out_row, d2, mx);
+    }
+    hipLaunchKernelGGL(pb_bump, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_row, d2, mx, k, possibility);
+    if (dims_mask) hipLaunchKernelGGL(pb_mean_seq, dim3((unsigned)n_active), dim3(256), 0, st, out_pts, k, mean);
+    hipLaunchKernelGGL(pb_apply, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_pts, k, dims_mask, mean, out_row, extra, n_extra,
+                       feat_bias, feat_scale, out_features);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}

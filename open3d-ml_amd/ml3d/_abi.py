@@ -73,6 +73,7 @@ SYMBOLS = [
     "ml3d_nearest_to_center_dev",
     "ml3d_patch_crop",
     "ml3d_patch_recenter",
+    "ml3d_possibility_argmin_workspace_bytes", "ml3d_possibility_argmin", "ml3d_patch_batch_workspace_bytes", "ml3d_patch_batch",
     "ml3d_vote_update",
     "ml3d_randla_gather_max",
     "ml3d_randla_gather_max_backward",
@@ -249,6 +250,14 @@ def bind(lib):
     lib.ml3d_patch_crop.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, sz, vp]
     lib.ml3d_patch_recenter.restype = C.c_int
     lib.ml3d_patch_recenter.argtypes = [vp, i64, i32, vp, i32, f32, f32, vp, vp, sz, vp]
+    lib.ml3d_possibility_argmin_workspace_bytes.restype = sz
+    lib.ml3d_possibility_argmin_workspace_bytes.argtypes = [i64, i64]
+    lib.ml3d_possibility_argmin.restype = C.c_int
+    lib.ml3d_possibility_argmin.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, sz, vp]
+    lib.ml3d_patch_batch_workspace_bytes.restype = sz
+    lib.ml3d_patch_batch_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.ml3d_patch_batch.restype = C.c_int
+    lib.ml3d_patch_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
     lib.ml3d_randla_gather_max.restype = C.c_int
     lib.ml3d_randla_gather_max.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp]
     lib.ml3d_randla_gather_max_backward.restype = C.c_int

@@ -94,6 +94,103 @@ def device_patch(points, possibility, center_index, perm, k, recenter_dims=(), e
     return pts, feats, sel
 
 
+def _host_splits(cloud_row_splits, active, what):
+    """The two HOST arrays of the multi-cloud entries: int64 row splits [C + 1] and the int32 list of active slots."""
+    splits = np.ascontiguousarray(cloud_row_splits.cpu().numpy() if isinstance(cloud_row_splits, torch.Tensor) else cloud_row_splits,
+                                  dtype=np.int64).reshape(-1)
+    n_clouds = splits.size - 1
+    act = np.arange(n_clouds, dtype=np.int32) if active is None else \
+        np.ascontiguousarray(active.cpu().numpy() if isinstance(active, torch.Tensor) else active, dtype=np.int32).reshape(-1)
+    if n_clouds < 1 or act.size < 1 or splits[0] != 0 or np.any(np.diff(splits) < 0) or act.min() < 0 or act.max() >= n_clouds or \
+            np.any(np.diff(act) <= 0):
+        raise RuntimeError(what + ": cloud_row_splits must be monotone from 0, active a strictly ascending list of its slots")
+    return splits, act
+
+
+def possibility_argmin(possibility, cloud_row_splits, active=None, out=None):
+    """Per cloud of a concatenated float64 ``possibility`` [N] (clouds delimited by the HOST ``cloud_row_splits`` [C + 1]): the
+    FIRST index of its minimum (cloud-local, ``torch.argmin`` order) and the minimum -- (int32 [C], float64 [C]) device tensors,
+    written for the slots of the HOST list ``active`` only (default: all; other entries of ``out`` are left as they are).
+    Deterministic, two launches, nothing read back: the minima are the multi-cloud loop's one read-back per round."""
+    lib = _abi.get()
+    _need_gpu(possibility)
+    splits, act = _host_splits(cloud_row_splits, active, "possibility_argmin")
+    n_clouds = splits.size - 1
+    dev = possibility.device
+    if possibility.dtype != torch.float64 or not possibility.is_contiguous() or possibility.dim() != 1 or \
+            possibility.numel() != int(splits[-1]) or np.any(np.diff(splits)[act] < 1):
+        raise RuntimeError("possibility_argmin: contiguous float64 [N] possibilities, N == cloud_row_splits[-1], no empty active cloud")
+    if out is None:
+        idx = torch.empty(n_clouds, dtype=torch.int32, device=dev)
+        mins = torch.empty(n_clouds, dtype=torch.float64, device=dev)
+    else:
+        idx, mins = out
+        if idx.dtype != torch.int32 or mins.dtype != torch.float64 or idx.numel() != n_clouds or mins.numel() != n_clouds or \
+                not (idx.is_contiguous() and mins.is_contiguous()):
+            raise RuntimeError("possibility_argmin: out = (int32 [C], float64 [C]), contiguous")
+    m = int(np.diff(splits)[act].sum())
+    wsb = lib.ml3d_possibility_argmin_workspace_bytes(m, act.size)
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_possibility_argmin(possibility.data_ptr(), splits.ctypes.data, n_clouds, act.ctypes.data, act.size,
+                                         idx.data_ptr(), mins.data_ptr(), ws.data_ptr(), wsb, _stream())
+    _abi.check(rc, "ml3d_possibility_argmin")
+    return idx, mins
+
+
+def device_patch_batch(points, possibility, cloud_row_splits, active, center_index, perm, k, recenter_dims=(), extra=None,
+                       feat_bias=0.0, feat_scale=1.0, out=None):
+    """One ROUND of the spatially regular patch loop for the A active clouds of a concatenated set (``device_patch`` for several
+    clouds in lock step): ``points`` float32 [N, 3], ``possibility`` float64 [N] (bumped IN PLACE), HOST ``cloud_row_splits``
+    [C + 1] and HOST ``active`` slot list (None: all), ``center_index`` DEVICE int32 [C] (``possibility_argmin``), ``perm`` DEVICE
+    int32 [A, k] (row a: the a-th active cloud's own host-drawn shuffle of 0..k-1), ``extra`` optional float32 [N, c].
+    Returns (points [A, k, 3] recentred on ``recenter_dims``, features [A, k, 3 + c], cloud-local indices int32 [A, k], rows of
+    the concatenated arrays int32 [A, k]); every item is bit for bit what ``device_patch`` gives on its cloud alone.
+    ``out``: the four tensors preallocated."""
+    lib = _abi.get()
+    _need_gpu(points, possibility, center_index, perm)
+    splits, act = _host_splits(cloud_row_splits, active, "device_patch_batch")
+    n_clouds, A, k = splits.size - 1, int(act.size), int(k)
+    dev = points.device
+    n = int(splits[-1])
+    if points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3) or possibility.dtype != torch.float64 or \
+            not possibility.is_contiguous() or possibility.numel() != n or center_index.dtype != torch.int32 or \
+            center_index.numel() != n_clouds or not center_index.is_contiguous() or perm.dtype != torch.int32 or \
+            tuple(perm.shape) != (A, k) or not perm.is_contiguous() or k < 1 or np.any(np.diff(splits)[act] < k):
+        raise RuntimeError("device_patch_batch: float32 [N, 3] points, float64 [N] possibilities, N == cloud_row_splits[-1], int32 [C] "
+                           "centre indices, int32 [A, k] permutations, 1 <= k <= every active cloud's size")
+    n_extra = 0
+    if extra is not None:
+        if extra.dtype != torch.float32 or not extra.is_contiguous() or extra.dim() != 2 or extra.shape[0] != n:
+            raise RuntimeError("device_patch_batch: extra must be a contiguous float32 [N, c] tensor")
+        _need_gpu(extra)
+        n_extra = int(extra.shape[1])
+    if out is None:
+        pts = torch.empty((A, k, 3), dtype=torch.float32, device=dev)
+        feats = torch.empty((A, k, 3 + n_extra), dtype=torch.float32, device=dev)
+        sel = torch.empty((A, k), dtype=torch.int32, device=dev)
+        row = torch.empty((A, k), dtype=torch.int32, device=dev)
+    else:
+        pts, feats, sel, row = out
+        if tuple(pts.shape) != (A, k, 3) or tuple(feats.shape) != (A, k, 3 + n_extra) or tuple(sel.shape) != (A, k) or \
+                tuple(row.shape) != (A, k) or pts.dtype != torch.float32 or feats.dtype != torch.float32 or sel.dtype != torch.int32 or \
+                row.dtype != torch.int32 or not (pts.is_contiguous() and feats.is_contiguous() and sel.is_contiguous() and row.is_contiguous()):
+            raise RuntimeError("device_patch_batch: out = (float32 [A, k, 3], float32 [A, k, 3 + c], int32 [A, k], int32 [A, k]), contiguous")
+    mask = 0
+    for d in recenter_dims:
+        mask |= 1 << int(d)
+    m = int(np.diff(splits)[act].sum())
+    wsb = lib.ml3d_patch_batch_workspace_bytes(m, A, k)
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_patch_batch(points.data_ptr(), possibility.data_ptr(), splits.ctypes.data, n_clouds, act.ctypes.data, A,
+                                  center_index.data_ptr(), perm.data_ptr(), k, mask, None if extra is None else extra.data_ptr(),
+                                  n_extra, float(feat_bias), float(feat_scale), pts.data_ptr(), feats.data_ptr(), sel.data_ptr(),
+                                  row.data_ptr(), ws.data_ptr(), wsb, _stream())
+    _abi.check(rc, "ml3d_patch_batch")
+    return pts, feats, sel, row
+
+
 def argmax_labels(scores, out=None):
     """uint8 labels [...] = argmax over the last axis of float32 ``scores`` [..., C <= 256] (first maximum, like
     torch.argmax) -- one pass over the scores instead of torch's generic reduction + dtype cast."""

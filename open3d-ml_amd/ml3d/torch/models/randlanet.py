@@ -496,7 +496,7 @@ class RandLANet(nn.Module):
     # arithmetic and ORDER (ml3d_patch_crop, ml3d_patch_recenter), and the only host input per patch is the shuffle of 0..k-1,
     # which depends on no data (``rng.permutation(idxs) == idxs[rng.permutation(k)]``: same draws) and is uploaded.  Patches are
     # identical to the host loop's, index for index (tests/test_gpu_api.py).
-    def _device_loop_state(self, data):
+    def _device_loop_state(self, data, possibility=None):
         cfg = self.cfg
         aug = dict(cfg.get('augment', {}) or {})
         norm = dict(aug.get('normalize', None) or {})
@@ -512,7 +512,7 @@ class RandLANet(nn.Module):
         rec = aug.get('recenter', None)
         nf = norm.get('feat', {}) if norm else {}
         return dict(points=tree._pts(), feat=feat, label=torch.from_numpy(np.ascontiguousarray(data['label'])).to(dev).long(),
-                    possibility=torch.from_numpy(self.possibility).to(dev), data=data,
+                    possibility=torch.from_numpy(self.possibility if possibility is None else possibility).to(dev), data=data,
                     dims=tuple(rec.get('dim', [0, 1, 2])) if rec else (), bias=float(nf.get('bias', 0)), scale=float(nf.get('scale', 1)))
 
     def _device_loop_serves(self, data, sampler):
@@ -683,6 +683,174 @@ class RandLANet(nn.Module):
             self.inference_result = {'predict_labels': pred_labels, 'predict_scores': probs[self.inference_proj_inds]}
             return True
         return False
+
+    # ---- several clouds in flight: one patch of EVERY active cloud per round, one forward at batch A -------------------------------
+    # The single-cloud loop above is a chain of small dependent launches per patch (an 8-pass sort of one cloud, one workgroup
+    # adding num_points floats in order) with a blocking read of the minimum possibility after every patch; the forward runs at
+    # batch 1.  A cloud's patches depend only on its own possibilities and its own shuffle draws -- never on a logit -- so C clouds
+    # can advance in lock step and each still produces exactly the patch sequence it produces alone (tests/test_emulated_multicloud.py).
+    def inference_many(self, clouds, seeds=None, max_in_flight=16, on_batch=None):
+        """Segment a list of raw clouds (dicts as ``inference_begin`` takes) with up to ``max_in_flight`` of them advancing in lock
+        step: per round ONE argmin + ONE read-back of the minima (the finished test), one batched sampler call
+        (``ops.device_patch_batch``), one neighbour pyramid over [A, k, 3], one forward at batch A and one vote update into a
+        concatenated float16 accumulator.  Returns ``[{'predict_labels', 'predict_scores'}, ...]`` in input order.
+
+        Cloud i has its OWN generator ``np.random.default_rng(seeds[i])`` (``seeds=None``: drawn from ``self.rng``) that gives its
+        possibilities and then one ``permutation(num_points)`` per patch -- the draws, in the order, of a single-cloud
+        ``RandLANet(seed=seeds[i])`` run, so patches, possibilities and the number of patches are that run's.
+        ``on_batch(slots, inputs, logits)`` is called after every forward: ``slots[b]`` = index into ``clouds`` of batch row b,
+        ``inputs`` the batch in the batcher's layout (device tensors), ``logits`` [A, k, classes].
+        A cloud the device loop cannot serve (fewer points than ``num_points`` after preprocessing, an augmentation it does not
+        know) runs through the single-cloud loop on its own afterwards, with its generator.
+        ``self.inference_many_info[i]`` keeps, per cloud, ``num_patches`` and its final ``possibility`` (numpy float64)."""
+        cfg, dev = self.cfg, self.device
+        _abi.require_gpu(dev, "RandLANet.inference_many")
+        if self.training:
+            raise RuntimeError("RandLANet.inference_many: call model.eval() first")
+        n_clouds = len(clouds)
+        S = int(max_in_flight)
+        if S < 1 or S > 256:
+            raise ValueError("RandLANet.inference_many: 1 <= max_in_flight <= 256")
+        if seeds is None:
+            seeds = [int(s) for s in self.rng.integers(0, 2 ** 63 - 1, size=n_clouds)]
+        if len(seeds) != n_clouds:
+            raise ValueError("RandLANet.inference_many: one seed per cloud")
+        self.test_smooth = 0.95
+        k, C_ = int(cfg.num_points), int(cfg.num_classes)
+        results = [None] * n_clouds
+        info = self.inference_many_info = [None] * n_clouds
+        host_path = []
+        waiting = iter(range(n_clouds))
+
+        def admit_next():
+            """State of the next cloud the device loop serves, created as inference_begin creates it (None: no cloud is left)."""
+            for i in waiting:
+                data = self.preprocess(clouds[i], {'split': 'test'})
+                rng = np.random.default_rng(seeds[i])
+                n = data['search_tree'].data.shape[0]
+                st = self._device_loop_state(data, rng.random(n) * 1e-3)
+                if st is None:
+                    host_path.append(i)
+                    continue
+                st.update(cloud=i, rng=rng, proj_inds=data['proj_inds'], n=int(n), patches=0,
+                          votes=torch.zeros((n, C_), dtype=torch.float16, device=dev))
+                return st
+            return None
+
+        slots = []                 # per slot: the cloud's state (None once retired); the buffers below are their concatenation
+        buf = {}
+
+        def rebuild():
+            """Concatenated device arrays of the clouds in the slots (one copy per array): a newly admitted cloud brings its own
+            tensors, the others are views of the previous buffers.  A retired slot keeps no rows."""
+            for s_, st in enumerate(slots):
+                if st is not None and 'points' not in st:        # lives in the old buffers
+                    a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
+                    st.update(points=buf['points'][a:b], possibility=buf['possibility'][a:b], label=buf['label'][a:b],
+                              votes=buf['votes'][a:b], feat=None if buf['feat'] is None else buf['feat'][a:b])
+            live = [st for st in slots if st is not None]
+            splits = np.zeros(len(slots) + 1, np.int64)
+            np.cumsum([0 if st is None else st['n'] for st in slots], out=splits[1:])
+            new = dict(splits=splits, feat=None)
+            for name in ('points', 'possibility', 'label', 'votes'):
+                new[name] = torch.cat([st[name] for st in live]).contiguous()
+            if live[0]['feat'] is not None:
+                new['feat'] = torch.cat([st['feat'] for st in live]).contiguous()
+            for st in live:
+                for name in ('points', 'possibility', 'label', 'votes', 'feat'):
+                    st.pop(name, None)
+            buf.clear()
+            buf.update(new)
+
+        def retire(s_):
+            st = slots[s_]
+            a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
+            probs = buf['votes'][a:b].cpu().numpy()
+            results[st['cloud']] = {'predict_labels': np.argmax(probs, 1)[st['proj_inds']], 'predict_scores': probs[st['proj_inds']]}
+            info[st['cloud']] = dict(num_patches=st['patches'], possibility=buf['possibility'][a:b].cpu().numpy())
+            slots[s_] = None
+
+        while len(slots) < S:
+            st = admit_next()
+            if st is None:
+                break
+            slots.append(st)
+        if slots:
+            rebuild()
+            idx = torch.zeros(len(slots), dtype=torch.int32, device=dev)
+            mins = torch.zeros(len(slots), dtype=torch.float64, device=dev)
+            perm_pinned = torch.empty((len(slots), k), dtype=torch.int32).pin_memory()
+            perm_dev = torch.empty((len(slots), k), dtype=torch.int32, device=dev)
+            uploaded = torch.cuda.Event()
+            uploaded.record()
+        active = [s_ for s_, st in enumerate(slots) if st is not None]
+        while active:
+            ops.possibility_argmin(buf['possibility'], buf['splits'], active, out=(idx, mins))
+            mins_host = mins.cpu().numpy()                           # the ONE read-back of the round
+            finished = [s_ for s_ in active if mins_host[s_] > 0.5]
+            if finished:
+                admitted = False
+                for s_ in finished:
+                    retire(s_)
+                    st = admit_next()
+                    if st is not None:
+                        slots[s_] = st
+                        admitted = True
+                active = [s_ for s_, st in enumerate(slots) if st is not None]
+                if not active:
+                    break
+                if admitted:
+                    rebuild()                                        # one device copy per admission, not per round
+                    # (a fresh cloud's possibilities are < 1e-3: nothing to read back, only its centre is needed)
+                    ops.possibility_argmin(buf['possibility'], buf['splits'], active, out=(idx, mins))
+            A = len(active)
+            # the A shuffles go up in ONE copy out of a pinned staging buffer whose previous upload has finished (see the note in
+            # _transform_device about asynchronous copies out of pageable memory)
+            uploaded.synchronize()
+            for a, s_ in enumerate(active):
+                slots[s_]['patches'] += 1
+                perm_pinned[a].copy_(torch.from_numpy(slots[s_]['rng'].permutation(k).astype(np.int32)))
+            perm_dev[:A].copy_(perm_pinned[:A], non_blocking=True)
+            uploaded.record()
+            first = slots[active[0]]
+            pts, feats, sel, row = ops.device_patch_batch(buf['points'], buf['possibility'], buf['splits'], active, idx, perm_dev[:A], k,
+                                                          first['dims'], buf['feat'], first['bias'], first['scale'])
+            nbr, itp = ops.randla_knn_pyramid(pts, cfg.sub_sampling_ratio, cfg.num_neighbors)
+            labels = buf['label'][row.long()]
+            inputs, coords, n = dict(), [], k
+            for i in range(cfg.num_layers):
+                coords.append(pts[:, :n])
+                n = n // cfg.sub_sampling_ratio[i]
+            inputs['coords'] = coords
+            inputs['neighbor_indices'] = nbr
+            inputs['sub_idx'] = [_mark_prefix(nbr[i][:, :k // int(np.prod(cfg.sub_sampling_ratio[:i + 1]))]) for i in range(cfg.num_layers)]
+            inputs['interp_idx'] = itp
+            inputs['features'] = feats
+            inputs['point_inds'] = sel
+            inputs['labels'] = labels
+            logits = self(inputs)
+            # rows of different clouds are distinct and a cloud's k nearest are distinct: the indices of this ONE call are distinct
+            ops.vote_update(buf['votes'], row.reshape(-1), logits.reshape(-1, C_), self.test_smooth)
+            if on_batch is not None:
+                on_batch([slots[s_]['cloud'] for s_ in active], inputs, logits)
+        # what the device loop cannot serve: the single-cloud loop, cloud by cloud, each with its own generator
+        keep_rng = self.rng
+        try:
+            for i in host_path:
+                self.rng = np.random.default_rng(seeds[i])
+                self.inference_begin(clouds[i])
+                count = 0
+                while True:
+                    inp = self.inference_preprocess()
+                    count += 1
+                    if self.inference_end(inp, self(inp['data'])):
+                        break
+                results[i] = self.inference_result
+                st = getattr(self, '_dev_loop', None)
+                info[i] = dict(num_patches=count, possibility=np.array(self.possibility) if st is None else st['possibility'].cpu().numpy())
+        finally:
+            self.rng = keep_rng
+        return results
 
     def get_optimizer(self, cfg_pipeline):
         """randlanet.py:352-357."""
