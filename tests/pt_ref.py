@@ -181,14 +181,17 @@ def make_state_dict(model_cfg, seed, shapes=None):
 
 
 # ---- direct torch-CPU formulas of the fused ops (unfolded parameters are the caller's; these take the folded layout) ----------
-def attention_formula(qkv, points, idx, a, ep=None):
+def attention_formula(qkv, points, idx, a, ep=None, rows=None):
+    """``rows`` = range(lo, hi): only those query rows (a large case is evaluated in chunks of rows)."""
     import torch
+    lo, hi = (0, idx.shape[0]) if rows is None else (rows.start, rows.stop)
+    idx = idx[lo:hi]
     n, ns = idx.shape
     c = qkv.shape[1] // 3
     s = c // 8
     flat = idx.reshape(-1).long()
-    q, k, v = qkv[:, :c], qkv[flat][:, c:2 * c].view(n, ns, c), qkv[flat][:, 2 * c:].view(n, ns, c)
-    d = points[flat].view(n, ns, 3) - points[:, None, :]
+    q, k, v = qkv[lo:hi, :c], qkv[flat][:, c:2 * c].view(n, ns, c), qkv[flat][:, 2 * c:].view(n, ns, c)
+    d = points[flat].view(n, ns, 3) - points[lo:hi, None, :]
     h = torch.relu(d @ a["p_w1"].t() + a["p_b1"])
     r = h @ a["p_w2t"] + a["p_b2"]
     u = torch.relu((k - q[:, None, :] + r) * a["w_scale0"] + a["w_shift0"])
@@ -201,8 +204,11 @@ def attention_formula(qkv, points, idx, a, ep=None):
     return out if ep is None else torch.relu(out * ep[0] + ep[1])
 
 
-def transition_down_formula(feat, points, sample_idx, idx, w_f_t, w_x, scale, shift):
+def transition_down_formula(feat, points, sample_idx, idx, w_f_t, w_x, scale, shift, rows=None):
+    """``rows`` = range(lo, hi): only those sampled rows."""
     import torch
+    lo, hi = (0, idx.shape[0]) if rows is None else (rows.start, rows.stop)
+    idx, sample_idx = idx[lo:hi], sample_idx[lo:hi]
     m, ns = idx.shape
     flat = idx.reshape(-1).long()
     d = points[flat].view(m, ns, 3) - points[sample_idx.long()][:, None, :]
@@ -211,9 +217,11 @@ def transition_down_formula(feat, points, sample_idx, idx, w_f_t, w_x, scale, sh
 
 
 def interpolate_formula(a, b, idx, d2):
+    """``a`` = None: the interpolation alone."""
+    import torch
     rec = 1.0 / (d2 + 1e-8)
     w = rec / rec.sum(1, keepdim=True)
-    out = a.clone()
+    out = torch.zeros(idx.shape[0], b.shape[1], dtype=b.dtype) if a is None else a.clone()
     for t in range(idx.shape[1]):
         out = out + b[idx[:, t].long()] * w[:, t:t + 1]
     return out

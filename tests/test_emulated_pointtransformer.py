@@ -6,7 +6,10 @@ Python wrappers (``ml3d.ops.pointtransformer``, the ``PointTransformer`` class) 
   tie between the two best candidates and the edge cases;
 * the fused attention, TransitionDown and interpolation kernels against direct torch-CPU formulas, <= 1e-5;
 * the whole ``pointtransformer_small`` forward against the reference's logits, <= 1e-4, FPS / k-NN indices exact, and the
-  state-dict layout equal to the reference's."""
+  state-dict layout equal to the reference's;
+* the bodies of tests/pt_cases.py that tests/test_gpu_pointtransformer_ops.py runs on the MI355X, here for every case of at
+  most 1025 points (and the furthest-point-sampling cases, which are cheap at any size): floats against the float64 formula
+  within max(1e-5, 4 e32), everything else for equality.  This run is where those bodies themselves get debugged."""
 import os
 import subprocess
 import sys
@@ -14,6 +17,7 @@ import sys
 import pytest
 
 import emu
+import pt_cases as C      # (the shape tables only: the bodies run in the subprocess)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(not emu.available(), reason="clang++ for the host emulator not found")
@@ -192,3 +196,51 @@ print("small forward: max|dlogit| = %%.3g, logit scale %%.2f, labels differing %
 assert out.shape == g["logits"].shape and err <= 1e-4, err
 ''' % ())
     assert "small forward" in out
+
+
+# ---- the bodies of tests/pt_cases.py (shared with tests/test_gpu_pointtransformer_ops.py) ------------------------------------------
+def _case(body):
+    out = _run("import pt_cases as C\n" + body + "\nprint('cases ok')\n")
+    assert "cases ok" in out
+    return out
+
+
+@pytest.mark.parametrize("c", C.ATTENTION_WIDTHS)
+def test_cases_attention_every_instantiation_against_float64(c):
+    out = _case("for ns in C.NSAMPLES:\n    C.check_attention_widths('cpu', %d, ns)" % c)
+    assert out.count("max_abs_delta") == 4
+
+
+def test_cases_attention_tiny_clamping_row_independence_refusals():
+    _case("C.check_attention_tiny('cpu')\nC.check_attention_clamping('cpu')\nC.check_attention_row_independence('cpu')\n"
+          "C.check_attention_refusals('cpu')")
+
+
+@pytest.mark.parametrize("c,cout,ns", C.DOWN_SHAPES)
+def test_cases_transition_down_against_float64(c, cout, ns):
+    _case("C.check_transition_down('cpu', %d, %d, %d)" % (c, cout, ns))
+
+
+def test_cases_transition_down_clamping_and_interpolate_short_item_and_refusals():
+    _case("C.check_transition_down_clamping_and_refusal('cpu')\nC.check_interpolate_short_item_and_refusal('cpu')")
+
+
+@pytest.mark.parametrize("c,k", C.INTERP_SHAPES)
+def test_cases_interpolate_against_float64(c, k):
+    _case("C.check_interpolate('cpu', %d, %d)" % (c, k))
+
+
+def test_cases_grid_stride_loops_at_the_narrow_width():
+    """Beyond 1025 points, but cheap on the emulator at c = 32: the attention's grid of 6144 workgroups and the two grids capped
+    at 65 535 (c = 512 at n = 12 293 is left to the GPU)."""
+    _case("for c, ns in C.ATTENTION_GRID:\n    if c == 32:\n        C.check_attention_grid_stride('cpu', c, ns)\n"
+          "C.check_transition_down_grid_cap('cpu')\nC.check_interpolate_grid_cap('cpu')")
+
+
+def test_cases_fps_launch_classes_workspace_form_and_dense_ties():
+    _case("for length in C.FPS_BOUNDARIES:\n    C.check_fps_class_boundary('cpu', length)\n"
+          "C.check_fps_workspace_form('cpu')\nC.check_fps_dense_ties('cpu')")
+
+
+def test_cases_fps_full_samples():
+    _case("C.check_fps_full_samples('cpu', twice=False)")
