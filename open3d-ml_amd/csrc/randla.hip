@@ -20,6 +20,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "gemm.h"
 #include <gfx950_ops.h>
 #include "grid.h"
@@ -27,36 +29,18 @@
 
 namespace ml3d {
 
-// A/B switches (speed, never results): every ML3D_* variable this file understands is read ONCE, at the first forward call
-// of the process; the library keeps no other state.  (The variant tests run one process per setting.)
-struct Knobs {
-    bool attn_xcd, attn_split, dec_split, dec_fc1, mlp_shaped;
-    bool force_valu, no_fuse;
-    int linear;
-    int attn_grid, attn16_grid;
-    long long fuse_rows;
-};
-// The A/B switches of rounds 1-3 are settled (numbers in profiles/DESIGN_rounds_1_to_4.md §3.3, §9): XCD-aware tile walk, split score Linear, split
-// decoder, decoder-last + fc1 chain and shaped MLP chains are ON wherever their shape conditions hold; the generic VALU kernels
-// and the per-layer launches remain as the fallback for widths / sizes the MFMA kernels do not cover.  The product library
-// reads nothing from the environment (no process-wide state); only the tests' HOST EMULATOR build
-// (-DML3D_TEST_HOOKS) reads ML3D_RANDLA_FUSE_ROWS, once: the row count from which per-point chains fuse, lowered there so that
-// small levels reach the fused kernels.
-static const Knobs& knobs() {
-    static const Knobs k = [] {
-        Knobs v;
-        v.attn_xcd = v.attn_split = v.dec_split = v.dec_fc1 = v.mlp_shaped = true;
-        v.force_valu = v.no_fuse = false;
-        v.linear = 0;
-        v.attn_grid = 2560;
-        v.attn16_grid = 4096;
-        v.fuse_rows = 64 * 1024;
+// Which kernel runs for which layer is decided by the layer's shape alone (numbers behind each choice: profiles/DESIGN_rounds_1_to_4.md
+// §3.3, §9): the generic VALU kernels and the per-layer launches are the fallback for widths / sizes the MFMA kernels do not cover.
+// The product library reads nothing from the environment (no process-wide state).  There is ONE test hook: the
+// tests' HOST EMULATOR build (-DML3D_TEST_HOOKS) reads ML3D_RANDLA_FUSE_ROWS once per process -- the row count from which per-point
+// chains fuse, lowered there so that small levels reach the fused kernels.  The build-time macros below are the only A/B switches left.
+static int64_t fuse_rows() {
 #ifdef ML3D_TEST_HOOKS
-        if (const char* e = getenv("ML3D_RANDLA_FUSE_ROWS")) v.fuse_rows = atoll(e);
+    static const int64_t rows = [] { const char* e = getenv("ML3D_RANDLA_FUSE_ROWS"); return e ? (int64_t)atoll(e) : (int64_t)64 * 1024; }();
+    return rows;
+#else
+    return 64 * 1024;
 #endif
-        return v;
-    }();
-    return k;
 }
 
 // A/B switch (build time, tools/build_variant.sh): which attention stages run on the bf16 matrix pipe (three-way split).
@@ -456,6 +440,30 @@ static int device_cu_count() {
         cus < 1)
         cus = 256;
     return cus;
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a run-time bool picks a template instance (ORD, SPLIT, EPI)
+template <class F>
+static int with_flag(bool v, F f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
+// when the launch below raises the kernel's dynamic-LDS limit first (each launcher keeps the rule it was measured with)
+enum class SetLds { Never, Above48K, Always };
+
+// One launch of an attention kernel that walks `tiles` tiles: min(ceil(tiles / tiles_per_wg), grid_cap) workgroups of `block`
+// threads with `lds` bytes of dynamic LDS.  The tiles are cut into per-XCD chunks of ~one cloud (xcd_tile) -- a.m_total / a.n
+// clouds -- and the grid is then rounded to the 8 XCDs.  `extra`: the kernel's arguments after the LfaArgs.
+template <class Kern, class... Extra>
+static int launch_attn_tiles(Kern kern, LfaArgs a, int64_t tiles, int tiles_per_wg, int64_t grid_cap, int block, size_t lds,
+                             SetLds set_lds, hipStream_t st, Extra... extra) {
+    const int64_t want = (tiles + tiles_per_wg - 1) / tiles_per_wg;
+    unsigned grid = (unsigned)(want < grid_cap ? want : grid_cap);
+    a.xcd_chunk = xcd_chunk_tiles(tiles, a.n > 0 ? a.m_total / a.n : 0);
+    if (a.xcd_chunk > 0) grid = (grid + 7u) & ~7u;
+    if ((set_lds == SetLds::Always || (set_lds == SetLds::Above48K && lds > 48 * 1024)) &&
+        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return ML3D_E_LAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, st, a, extra...);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
 #define SYNC_ATTN() block_sync_lds()   // LDS-only workgroup barrier (grid.h): global loads / stores stay in flight
@@ -1104,22 +1112,15 @@ __global__ void __launch_bounds__((WaveAttnCfg<D>::W * 64)) lfa_attn_wave(LfaArg
 template <int D, int STAGE>
 static int launch_attn_wave(LfaArgs a, hipStream_t st) {
     using C = WaveAttnCfg<D>;
-    const int64_t tiles = (a.m_total + 1) / 2;
     static const int cus = device_cu_count();
-    int64_t blocks = (tiles + C::W - 1) / C::W;
-    unsigned grid = (unsigned)(blocks < cus ? blocks : cus);     // one 12/16-wave workgroup per CU (LDS-bound)
-    const bool xcd_on = knobs().attn_xcd;
-    a.xcd_chunk = xcd_on ? xcd_chunk_tiles(tiles, a.n > 0 ? a.m_total / a.n : 0) : 0;
-    if (a.xcd_chunk > 0) grid = (grid + 7u) & ~7u;
     const size_t sm = sizeof(float) * ((size_t)C::WFLOATS + (size_t)C::W * C::PATCH);
-    auto go = [&](auto kern) -> int {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess)
-            return ML3D_E_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::W * 64), sm, st, a);
-        return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
-    };
-    if (a.gscore) return a.order ? go(lfa_attn_wave<D, STAGE, true, true>) : go(lfa_attn_wave<D, STAGE, true, false>);
-    return a.order ? go(lfa_attn_wave<D, STAGE, false, true>) : go(lfa_attn_wave<D, STAGE, false, false>);
+    return with_flag(a.gscore != nullptr, [&](auto split) {
+        return with_flag(a.order != nullptr, [&](auto ord) {
+            // 2-point tiles, one per wave; one 12/16-wave workgroup per CU (LDS-bound)
+            return launch_attn_tiles(lfa_attn_wave<D, STAGE, decltype(split)::value, decltype(ord)::value>, a, (a.m_total + 1) / 2,
+                                     C::W, cus, C::W * 64, sm, SetLds::Always, st);
+        });
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1489,18 +1490,11 @@ template <int D, int STAGE>
 static int launch_attn_b3(LfaArgs a, hipStream_t st) {
     using C = B3Cfg<D, STAGE>;
     static const int cus = device_cu_count();
-    const int64_t tiles = (a.m_total + C::TP - 1) / C::TP;
-    unsigned grid = (unsigned)(tiles < cus ? tiles : cus);       // one 8-wave workgroup per CU, weights split once per workgroup
-    a.xcd_chunk = knobs().attn_xcd ? xcd_chunk_tiles(tiles, a.n > 0 ? a.m_total / a.n : 0) : 0;
-    if (a.xcd_chunk > 0) grid = (grid + 7u) & ~7u;
-    const size_t sm = C::smem_bytes();
-    auto go = [&](auto kern) -> int {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess)
-            return ML3D_E_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), sm, st, a);
-        return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
-    };
-    return a.order ? go(lfa_attn_b3<D, STAGE, true>) : go(lfa_attn_b3<D, STAGE, false>);
+    return with_flag(a.order != nullptr, [&](auto ord) {
+        // one 8-wave workgroup per CU, weights split once per workgroup
+        return launch_attn_tiles(lfa_attn_b3<D, STAGE, decltype(ord)::value>, a, (a.m_total + C::TP - 1) / C::TP, 1, cus, C::THREADS,
+                                 C::smem_bytes(), SetLds::Always, st);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1795,28 +1789,25 @@ __global__ void __launch_bounds__((WaveB3Cfg<D>::W * 64)) lfa_attn_wave_b3(LfaAr
 template <int D, int STAGE>
 static int launch_attn_wave_b3(LfaArgs a, hipStream_t st) {
     using C = WaveB3Cfg<D>;
-    const int64_t tiles = (a.m_total + 1) / 2;
     static const int cus = device_cu_count();
-    int64_t blocks = (tiles + C::W - 1) / C::W;
-    unsigned grid = (unsigned)(blocks < cus ? blocks : cus);     // one 12-wave workgroup per CU (LDS-bound)
-    a.xcd_chunk = knobs().attn_xcd ? xcd_chunk_tiles(tiles, a.n > 0 ? a.m_total / a.n : 0) : 0;
-    if (a.xcd_chunk > 0) grid = (grid + 7u) & ~7u;
-    const size_t sm = C::smem_bytes();
-    auto go = [&](auto kern) -> int {
-        if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess)
-            return ML3D_E_LAUNCH;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(C::W * 64), sm, st, a);
-        return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
-    };
-    return a.order ? go(lfa_attn_wave_b3<D, STAGE, true>) : go(lfa_attn_wave_b3<D, STAGE, false>);
+    return with_flag(a.order != nullptr, [&](auto ord) {
+        // 2-point tiles, one per wave; one 12-wave workgroup per CU (LDS-bound)
+        return launch_attn_tiles(lfa_attn_wave_b3<D, STAGE, decltype(ord)::value>, a, (a.m_total + 1) / 2, C::W, cus, C::W * 64,
+                                 C::smem_bytes(), SetLds::Always, st);
+    });
 }
+
+// the layer widths that have an MFMA attention kernel
+template <int D>
+constexpr bool ATTN_MFMA_WIDTH = D == 16 || D == 32 || D == 64 || D == 128 || D == 256;
 
 // launches the attention part of one stage; `a.out` receives agg [m, D].  D <= 64: the per-wave kernel, D >= 128: the
 // workgroup-tile prefetching kernel.  (Preconditions -- 32-bit point indices, at least one full tile per cloud -- are checked
 // by the caller, which sends everything else to the generic VALU kernel lfa_stage.)
 template <int D>
 static bool attn_mfma_fits(const LfaArgs& a) {
-    return a.m_total < ((int64_t)1 << 30) && a.n0 < ((int64_t)1 << 30) && (D <= 64 || a.n >= MfmaCfg<D>::TP);
+    if constexpr (!ATTN_MFMA_WIDTH<D>) return false;
+    else return a.m_total < ((int64_t)1 << 30) && a.n0 < ((int64_t)1 << 30) && (D <= 64 || a.n >= MfmaCfg<D>::TP);
 }
 
 template <int D, int STAGE>
@@ -1832,21 +1823,14 @@ static int launch_attn_mfma(LfaArgs a, hipStream_t st) {
             if (a.gscore && a.n >= B3Cfg<D, 1>::TP) return launch_attn_b3<D, STAGE>(a, st);     // (the caller put the score bias into gscore)
         }
         using C = MfmaCfg<D>;
-        const int grid_cap = knobs().attn_grid;   // tuning knob
-        int64_t tiles = (a.m_total + C::TP - 1) / C::TP;
-        unsigned grid = (unsigned)(tiles < grid_cap ? tiles : grid_cap);   // persistent-ish: weights load once per block
-        a.xcd_chunk = knobs().attn_xcd ? xcd_chunk_tiles(tiles, a.n > 0 ? a.m_total / a.n : 0) : 0;
-        if (a.xcd_chunk > 0) grid = (grid + 7u) & ~7u;
-        const size_t sm = pf_smem_bytes<D, STAGE>();
-        auto go = [&](auto kern) -> int {
-            if (sm > 48 * 1024 &&
-                hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess)
-                return ML3D_E_LAUNCH;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), sm, st, a);
-            return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
-        };
-        if (a.gscore) return a.order ? go(lfa_attn_pf<D, STAGE, true, true>) : go(lfa_attn_pf<D, STAGE, true, false>);
-        return a.order ? go(lfa_attn_pf<D, STAGE, false, true>) : go(lfa_attn_pf<D, STAGE, false, false>);
+        constexpr int ATTN_GRID = 2560;           // tuning knob.  persistent-ish: weights load once per block
+        return with_flag(a.gscore != nullptr, [&](auto split) {
+            return with_flag(a.order != nullptr, [&](auto ord) {
+                return launch_attn_tiles(lfa_attn_pf<D, STAGE, decltype(split)::value, decltype(ord)::value>, a,
+                                         (a.m_total + C::TP - 1) / C::TP, 1, ATTN_GRID, C::THREADS, pf_smem_bytes<D, STAGE>(),
+                                         SetLds::Above48K, st);
+            });
+        });
     }
 }
 
@@ -2156,18 +2140,22 @@ lfa_attn_mfma16(LfaArgs A, const float* __restrict__ lse1_wt, const float* __res
 // epilogue: the stage's per-point Linears inside the kernel (a.out = p1 [m, 8] / the layer output [m, 32]); needs a.d_in == 8
 template <int STAGE>
 static int launch_attn_mfma16(LfaArgs a, hipStream_t st, bool epilogue) {
-    int64_t tiles = (a.m_total + A16_TP - 1) / A16_TP;
-    const bool xcd_on = knobs().attn_xcd;
-    a.xcd_chunk = xcd_on ? xcd_chunk_tiles(tiles, a.n > 0 ? a.m_total / a.n : 0) : 0;
-    const int cap = knobs().attn16_grid;
-    unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
-    if (a.xcd_chunk > 0) grid = (grid + 7u) & ~7u;
-    auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, a, a.lse1_wt, a.lse1_b, a.lse2_wt, a.lse2_b);
-    };
-    if (epilogue) { if (a.order) go(lfa_attn_mfma16<STAGE, true, true>); else go(lfa_attn_mfma16<STAGE, false, true>); }
-    else { if (a.order) go(lfa_attn_mfma16<STAGE, true, false>); else go(lfa_attn_mfma16<STAGE, false, false>); }
-    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+    constexpr int ATTN16_GRID = 4096;
+    return with_flag(a.order != nullptr, [&](auto ord) {
+        return with_flag(epilogue, [&](auto epi) {
+            return launch_attn_tiles(lfa_attn_mfma16<STAGE, decltype(ord)::value, decltype(epi)::value>, a,
+                                     (a.m_total + A16_TP - 1) / A16_TP, 1, ATTN16_GRID, 256, 0, SetLds::Never, st, a.lse1_wt, a.lse1_b,
+                                     a.lse2_wt, a.lse2_b);
+        });
+    });
+}
+
+// the attention stage at width D, for the levels attn_mfma_fits<D> accepts (`epi16`: see launch_attn_mfma16)
+template <int D, int STAGE>
+static int launch_attn(const LfaArgs& a, hipStream_t st, bool epi16) {
+    if constexpr (D == 16) return launch_attn_mfma16<STAGE>(a, st, epi16);
+    else if constexpr (ATTN_MFMA_WIDTH<D>) return launch_attn_mfma<D, STAGE>(a, st);
+    else return ML3D_E_UNSUPPORTED;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2199,6 +2187,22 @@ struct ChainArgs {
     float* out;
     int64_t m_total;
 };
+
+// The Linears lin[0 .. n), each reading its predecessor's output, as one chain: the first may gather its second input, a later
+// one's second input is the chain's `cat`.  The intermediate outputs are not written.
+static ChainArgs chain_of(const LinArgs* lin, int n) {
+    ChainArgs c = {};
+    c.a0 = lin[0].a0; c.c0 = lin[0].c0; c.a1 = lin[0].a1; c.c1 = lin[0].c1; c.gather = lin[0].gather;
+    c.rows_per_item = lin[0].rows_per_item; c.a1_rows_per_item = lin[0].a1_rows_per_item;
+    c.n_layers = n;
+    for (int l = 0; l < n; ++l) {
+        const LinArgs& a = lin[l];
+        if (l > 0 && a.a1) { c.cat = a.a1; c.cat_c = a.c1; c.cat_layer = l; }
+        c.L[l] = ChainLayer{a.wt, a.bias, a.bias2, a.c0 + (a.a1 ? a.c1 : 0), a.cout, a.act, a.slope};
+    }
+    c.out = lin[n - 1].out; c.m_total = lin[0].m_total;
+    return c;
+}
 
 // one 32x32 output tile's K loop with compile-time trip count and weight pitch
 template <int KH, int NP>
@@ -2661,7 +2665,7 @@ static int launch_mlp_chain_b3(const ChainArgs& a, hipStream_t st) {
 
 // multi-layer chains run fused iff their shape has a compiled per-wave instance (callers fall back to one Linear per layer)
 static bool chain_compiled(const ChainArgs& a) {
-    if (a.m_total <= 0 || !knobs().mlp_shaped) return false;
+    if (a.m_total <= 0) return false;
     return mlp_shape_matches<ShapeDecFc1>(a) || mlp_shape_matches<ShapeFc1>(a) || mlp_shape_matches<ShapeEnc64>(a) ||
            mlp_shape_matches<ShapeEnc16>(a);
 }
@@ -2681,9 +2685,6 @@ static int launch_chain_auto(const ChainArgs& a, hipStream_t st) {
     return ML3D_E_UNSUPPORTED;
 }
 
-// one Linear described by LinArgs: a shape-compiled per-wave kernel or the tile GEMM; the VALU kernel for K < 8
-static int launch_linear_auto(const LinArgs& a, hipStream_t st);
-
 template <int D, int STAGE>
 static size_t lfa_smem_bytes(int d_in) {
     using C = LfaCfg<D>;
@@ -2692,28 +2693,54 @@ static size_t lfa_smem_bytes(int d_in) {
     return f * 4 + (size_t)C::TP * RK * 4;
 }
 
+// the caller's ml3d_trace records (a chain through ->next): events around the launches that carry a record's tag
+struct Tracer {
+    const ml3d_trace* t;
+    hipStream_t st;
+    // rc = launch(), between the start and stop events of every record tagged `tag`
+    template <class F>
+    int traced(int tag, F launch) const {
+        for (const ml3d_trace* r = t; r; r = r->next)
+            if (r->tag == tag && r->ev_start) (void)hipEventRecord((hipEvent_t)r->ev_start, st);
+        const int rc = launch();
+        for (const ml3d_trace* r = t; r; r = r->next)
+            if (r->tag == tag && r->ev_stop) (void)hipEventRecord((hipEvent_t)r->ev_stop, st);
+        return rc;
+    }
+};
+
 template <int D>
-static int launch_lfa(const LfaArgs& a1, const LfaArgs& a2, hipStream_t st, const ml3d_trace* tr, int tag1) {
+static int launch_lfa(const LfaArgs& a1, const LfaArgs& a2, hipStream_t st, const Tracer& T, int tag1) {
     using C = LfaCfg<D>;
     int64_t tiles = (a1.m_total + C::TP - 1) / C::TP;
     unsigned grid = (unsigned)(tiles < 8192 ? tiles : 8192);
     size_t sm1 = lfa_smem_bytes<D, 1>(a1.d_in), sm2 = lfa_smem_bytes<D, 2>(a2.d_in);
     if (sm1 > 160 * 1024 || sm2 > 160 * 1024) return ML3D_E_UNSUPPORTED;
-    if (sm1 > 48 * 1024 &&
-        hipFuncSetAttribute((const void*)lfa_stage<D, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm1) != hipSuccess)
-        return ML3D_E_LAUNCH;
-    if (sm2 > 48 * 1024 &&
-        hipFuncSetAttribute((const void*)lfa_stage<D, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm2) != hipSuccess)
-        return ML3D_E_LAUNCH;
-    if (tr && tr->tag == tag1 && tr->ev_start) (void)hipEventRecord((hipEvent_t)tr->ev_start, st);
-    hipLaunchKernelGGL((lfa_stage<D, 1>), dim3(grid), dim3(LFA_THREADS), sm1, st, a1);
-    if (tr && tr->tag == tag1 && tr->ev_stop) (void)hipEventRecord((hipEvent_t)tr->ev_stop, st);
-    if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    if (tr && tr->tag == tag1 + 1 && tr->ev_start) (void)hipEventRecord((hipEvent_t)tr->ev_start, st);
-    hipLaunchKernelGGL((lfa_stage<D, 2>), dim3(grid), dim3(LFA_THREADS), sm2, st, a2);
-    if (tr && tr->tag == tag1 + 1 && tr->ev_stop) (void)hipEventRecord((hipEvent_t)tr->ev_stop, st);
-    if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    return 0;
+    auto stage = [&](int tag, auto kern, size_t sm, const LfaArgs& a) -> int {
+        if (sm > 48 * 1024 && hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess)
+            return ML3D_E_LAUNCH;
+        return T.traced(tag, [&] {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(LFA_THREADS), sm, st, a);
+            return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+        });
+    };
+    const int rc = stage(tag1, lfa_stage<D, 1>, sm1, a1);
+    return rc ? rc : stage(tag1 + 1, lfa_stage<D, 2>, sm2, a2);
+}
+
+// f(std::integral_constant<int, D>{}) for the layer width dd; widths without any attention kernel are unsupported
+template <class F>
+static int dispatch_width(int dd, F f) {
+    switch (dd) {
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        case 256: return f(std::integral_constant<int, 256>{});
+        case 512: return f(std::integral_constant<int, 512>{});
+        default: return ML3D_E_UNSUPPORTED;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2828,19 +2855,6 @@ attentive_pool_k(const float* __restrict__ scores, const float* __restrict__ x, 
     }
 }
 
-struct Tracer {
-    const ml3d_trace* t;
-    hipStream_t st;
-    void begin(int tag) const {
-        for (const ml3d_trace* r = t; r; r = r->next)
-            if (r->tag == tag && r->ev_start) (void)hipEventRecord((hipEvent_t)r->ev_start, st);
-    }
-    void end(int tag) const {
-        for (const ml3d_trace* r = t; r; r = r->next)
-            if (r->tag == tag && r->ev_stop) (void)hipEventRecord((hipEvent_t)r->ev_stop, st);
-    }
-};
-
 static int launch_linear(const LinArgs& a, hipStream_t st) {
     if (a.m_total <= 0) return 0;
     int64_t items = ((a.m_total + LIN_RM - 1) / LIN_RM) * a.cout;
@@ -2848,17 +2862,11 @@ static int launch_linear(const LinArgs& a, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
+// one Linear described by LinArgs: a shape-compiled per-wave kernel or the tile GEMM; the VALU kernel for K < 8
 static int launch_linear_auto(const LinArgs& a, hipStream_t st) {
-    // the register-prefetching tile GEMM of gemm.hip (lin_mode 2 = the scalar kernel: a settled A/B, Knobs::linear stays 0)
-    const int lin_mode = knobs().linear;
-    const bool shaped = knobs().mlp_shaped;
-    if (lin_mode == 0 && shaped && !a.a1 && a.m_total >= knobs().fuse_rows) {     // (tests lower the row threshold)
+    if (!a.a1 && a.m_total >= fuse_rows()) {     // (tests lower the row threshold)
         // narrow Linears over many rows: the barrier-free per-wave kernel with a compiled shape
-        ChainArgs c = {};
-        c.a0 = a.a0; c.c0 = a.c0; c.n_layers = 1;
-        c.L[0].wt = a.wt; c.L[0].bias = a.bias; c.L[0].bias2 = a.bias2; c.L[0].cin = a.c0; c.L[0].cout = a.cout;
-        c.L[0].act = a.act; c.L[0].slope = a.slope;
-        c.out = a.out; c.m_total = a.m_total;
+        const ChainArgs c = chain_of(&a, 1);
         if (a.cout == 8 && mlp_shape_matches<ShapeLin16x8>(c)) return launch_mlp_wave_s<ShapeLin16x8, 8>(c, st);
         if (a.cout == 8 && mlp_shape_matches<ShapeLin8x8>(c)) return launch_mlp_wave_s<ShapeLin8x8, 8>(c, st);
         if (a.cout == 32 && mlp_shape_matches<ShapeLin64x32>(c)) return launch_mlp_wave_s<ShapeLin64x32, 8>(c, st);
@@ -2876,7 +2884,7 @@ static int launch_linear_auto(const LinArgs& a, hipStream_t st) {
             if (rc != ML3D_E_UNSUPPORTED) return rc;
         }
     }
-    if (lin_mode != 2 && a.c0 + a.c1 >= 8) {
+    if (a.c0 + a.c1 >= 8) {       // the register-prefetching tile GEMM of gemm.hip
         RowsA A;
         A.a = a.a0; A.lda = a.c0; A.k1 = a.c0;
         A.gather = a.a1 ? a.gather : nullptr; A.gather_stride = 1; A.a_rows = a.a1_rows_per_item;
@@ -2886,6 +2894,20 @@ static int launch_linear_auto(const LinArgs& a, hipStream_t st) {
         return gemm_rows(A, a.wt, a.m_total, a.cout, a.c0 + A.k2, ep, a.out, a.cout, nullptr, 0, st);
     }
     return launch_linear(a, st);
+}
+
+// The Linears lin[0 .. n), each reading its predecessor's output, under the trace tags tag0, tag0 + 1, ..: ONE chain launch
+// (tag0) if `fuse` and their shape has a compiled chain kernel, else one launch each through the intermediate outputs
+static int launch_linears(const LinArgs* lin, int n, bool fuse, const Tracer& T, int tag0, hipStream_t st) {
+    if (fuse) {
+        const ChainArgs ch = chain_of(lin, n);
+        if (chain_compiled(ch)) return T.traced(tag0, [&] { return launch_chain_auto(ch, st); });
+    }
+    for (int l = 0; l < n; ++l) {
+        const int rc = T.traced(tag0 + l, [&] { return launch_linear_auto(lin[l], st); });
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 // ---- parameter layout ---------------------------------------------------------------------------
@@ -3033,9 +3055,6 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
     if (workspace_bytes < ml3d_randla_forward_workspace_bytes(d)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const Tracer T = {trace, st};
-    const bool force_valu = knobs().force_valu;                // (settled A/B switches of rounds 1-3, fixed false: the generic VALU
-    const bool no_fuse = knobs().no_fuse;                      //  kernels / one launch per Linear)
-    const int64_t fuse_rows = knobs().fuse_rows;               // tuning/test knob: rows from which pool2+mlp2 fuse
     const int Lr = d->num_layers;
     const int64_t B = d->batch;
     int64_t n[ML3D_RANDLA_MAX_LAYERS + 1];
@@ -3052,24 +3071,35 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
     // scratch for the bf16 planes of one weight matrix (deep Linears on the bf16 matrix pipe: launch_linear_auto)
     const size_t pack_bytes = lin_pack_bytes(d);
     void* pack_ws = take((int64_t)(pack_bytes + 3) / 4);
+    // one Linear of the forward: out [rows, cout] = act(bias (+ bias2) + [in | in1] . W), leaky relu of `slope` (0: none); the
+    // weights and biases are parameter slots (-1: no bias)
+    auto lin = [&](const float* in, int k, int w, int b, float* out, int64_t rows, int cout, float slope,
+                   const float* in1 = nullptr, int k1 = 0, int b2 = -1) {
+        LinArgs a = {};
+        a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
+        a.a0 = in; a.c0 = k; a.a1 = in1; a.c1 = k1;
+        a.wt = P(w); a.bias = b >= 0 ? P(b) : nullptr; a.bias2 = b2 >= 0 ? P(b2) : nullptr;
+        a.out = out; a.m_total = rows; a.cout = cout; a.act = slope != 0.f; a.slope = slope;
+        return a;
+    };
+    auto run = [&](int tag, const LinArgs& a) { return T.traced(tag, [&] { return launch_linear_auto(a, st); }); };
+    int rc = 0;
     // fc0 + bn0 + lrelu(0.2)            (randlanet.py:266-271)
     float* feat = take(B * n[0] * d->dim_features);
     // every reference config: 8 features into a 16-wide first layer -> fc0 and that layer's mlp1 share one launch
     float* f1_head = nullptr;
-    if (!force_valu && !no_fuse && d->dim_features == 8 && d->dim_output[0] == 16) {
+    if (d->dim_features == 8 && d->dim_output[0] == 16) {
         f1_head = take(B * n[0] * 8);
         const int64_t m = B * n[0];
-        T.begin(1000);
-        hipLaunchKernelGGL(head_fc0_mlp1, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, features, d->in_channels, P(0), P(1),
-                           P(2), P(3), m, feat, f1_head);
-        T.end(1000);
-        if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
+        rc = T.traced(1000, [&] {
+            hipLaunchKernelGGL(head_fc0_mlp1, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, features, d->in_channels, P(0), P(1),
+                               P(2), P(3), m, feat, f1_head);
+            return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+        });
     } else {
-        LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-        a.a0 = features; a.c0 = d->in_channels; a.wt = P(0); a.bias = P(1); a.out = feat;
-        a.m_total = B * n[0]; a.cout = d->dim_features; a.act = 1; a.slope = 0.2f;
-        T.begin(1000); int rc = launch_linear_auto(a, st); T.end(1000); if (rc) return rc;
+        rc = run(1000, lin(features, d->in_channels, 0, 1, feat, B * n[0], d->dim_features, 0.2f));
     }
+    if (rc) return rc;
     int d_in = d->dim_features;
     float* enc_keep[ML3D_RANDLA_MAX_LAYERS + 1];   // encoder_feat_list (randlanet.py:274-283)
     for (int l = 0; l < Lr; ++l) {
@@ -3080,10 +3110,8 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
         float* enc = take(M * 2 * dd);
         float* samp = take(B * n[l + 1] * 2 * dd);
         if (!(l == 0 && f1_head)) {   // mlp1: SharedMLP(d_in, d/2) lrelu 0.2   (randlanet.py:680)
-            LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-            a.a0 = feat; a.c0 = d_in; a.wt = P(sb + 0); a.bias = P(sb + 1); a.out = f1;
-            a.m_total = M; a.cout = h; a.act = 1; a.slope = 0.2f;
-            T.begin(8 * l); int rc = launch_linear_auto(a, st); T.end(8 * l); if (rc) return rc;
+            rc = run(8 * l, lin(feat, d_in, sb + 0, sb + 1, f1, M, h, 0.2f));
+            if (rc) return rc;
         }
         LfaArgs s1 = {};
         s1.xyz = points; s1.nidx = neighbor_idx[l]; s1.n = n[l]; s1.n0 = n[0]; s1.m_total = M;
@@ -3096,127 +3124,72 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
         s2.score_wt = P(sb + 10); s2.score_b = P(sb + 11); s2.pool_wt = P(sb + 12); s2.pool_b = P(sb + 13);
         s2.mlp2_wt = P(sb + 14); s2.mlp2_b = P(sb + 16); s2.short_wt = P(sb + 15); s2.short_b = P(sb + 17);
         s2.feat_in = feat; s2.out = enc;
-        int rc = 0;
         // (the MFMA kernels keep point indices in 32 bits; a > 2^30-point batch level takes the generic VALU kernel)
-        const bool mfma_ok = !force_valu && (dd == 16 ? attn_mfma_fits<16>(s1) : dd == 32 ? attn_mfma_fits<32>(s1) :
-                                             dd == 64 ? attn_mfma_fits<64>(s1) : dd == 128 ? attn_mfma_fits<128>(s1) :
-                                             dd == 256 ? attn_mfma_fits<256>(s1) : false);
+        bool mfma_ok = false;
+        dispatch_width(dd, [&](auto w) { mfma_ok = attn_mfma_fits<decltype(w)::value>(s1); return 0; });
         if (mfma_ok) {
             float* agg = take(M * dd);
             float* p2 = take(M * dd);
             LfaArgs q1 = s1; q1.out = agg;
             // first layer of every reference config (16 wide, 8 features in): the per-point Linears behind both stages run
             // inside the attention kernels (lfa_attn_mfma16<.., EPI>), `agg` is never written
-            const bool epi16 = dd == 16 && d_in == 8 && !no_fuse;
+            const bool epi16 = dd == 16 && d_in == 8;
             if (epi16) q1.out = p1;
-            // D >= 128: the feature half of the score Linear once per POINT (gscore = f . W_top^T, into the p2 scratch,
+            // D >= 32: the feature half of the score Linear once per POINT (gscore = f . W_top^T, into the p2 scratch,
             // which is otherwise idle until pool2), gathered by the attention kernel instead of recomputed per neighbour
-            const bool split_on = knobs().attn_split;
-            const bool split = split_on && dd >= 32 && dd <= 256 && M * dd * 4 < ((int64_t)1 << 32) &&
-                               M < ((int64_t)1 << 30);
+            const bool split = dd >= 32 && dd <= 256 && M * dd * 4 < ((int64_t)1 << 32) && M < ((int64_t)1 << 30);
             // (the per-wave kernels of D <= 64 and the bf16x3 kernels of D = 128 / 256 take the score bias inside gscore, the f32
             //  workgroup kernels add it themselves)
             const bool b3_attn = ((ML3D_ATTN_B3) & 1) != 0 && split && ((dd == 128 && n[l] >= B3Cfg<128, 1>::TP) || (dd == 256 && n[l] >= B3Cfg<256, 1>::TP));
-            auto point_scores = [&](const float* gfeat, const float* score_wt, const float* score_b, int tag) -> int {
-                LinArgs ga = {}; ga.pack_ws = pack_ws; ga.pack_bytes = pack_bytes;
-                ga.a0 = gfeat; ga.c0 = h; ga.wt = score_wt; ga.bias = (dd <= 64 || b3_attn) ? score_b : nullptr; ga.out = p2;   // first h rows of [d][d]
-                ga.m_total = M; ga.cout = dd; ga.act = 0;
-                T.begin(tag);
-                const int r = launch_linear_auto(ga, st);
-                T.end(tag);
-                return r;
+            auto point_scores = [&](const float* gfeat, int score_w, int score_b) {      // first h rows of [d][d]
+                return run(8 * l + 7, lin(gfeat, h, score_w, (dd <= 64 || b3_attn) ? score_b : -1, p2, M, dd, 0.f));
             };
-            if (split) { rc = point_scores(f1, s1.score_wt, s1.score_b, 8 * l + 7); if (rc) return rc; q1.gscore = p2; }
-            T.begin(8 * l + 1);
-            switch (dd) {
-                case 16: rc = launch_attn_mfma16<1>(q1, st, epi16); break;
-                case 32: rc = launch_attn_mfma<32, 1>(q1, st); break;
-                case 64: rc = launch_attn_mfma<64, 1>(q1, st); break;
-                case 128: rc = launch_attn_mfma<128, 1>(q1, st); break;
-                default: rc = launch_attn_mfma<256, 1>(q1, st); break;
-            }
-            T.end(8 * l + 1);
+            if (split) { rc = point_scores(f1, sb + 4, sb + 5); if (rc) return rc; q1.gscore = p2; }
+            rc = T.traced(8 * l + 1, [&] {
+                return dispatch_width(dd, [&](auto w) { return launch_attn<decltype(w)::value, 1>(q1, st, epi16); });
+            });
             if (rc) return rc;
             if (!epi16) {   // pool1.mlp: SharedMLP(d, d/2) lrelu 0.2            (randlanet.py:639)
-                LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-                a.a0 = agg; a.c0 = dd; a.wt = P(sb + 6); a.bias = P(sb + 7); a.out = p1;
-                a.m_total = M; a.cout = h; a.act = 1; a.slope = 0.2f;
-                T.begin(8 * l + 4); rc = launch_linear_auto(a, st); T.end(8 * l + 4); if (rc) return rc;
+                rc = run(8 * l + 4, lin(agg, dd, sb + 6, sb + 7, p1, M, h, 0.2f));
+                if (rc) return rc;
             }
             LfaArgs q2 = s2; q2.out = epi16 ? enc : agg;
-            if (split) { rc = point_scores(p1, s2.score_wt, s2.score_b, 8 * l + 7); if (rc) return rc; q2.gscore = p2; }
-            T.begin(8 * l + 2);
-            switch (dd) {
-                case 16: rc = launch_attn_mfma16<2>(q2, st, epi16); break;
-                case 32: rc = launch_attn_mfma<32, 2>(q2, st); break;
-                case 64: rc = launch_attn_mfma<64, 2>(q2, st); break;
-                case 128: rc = launch_attn_mfma<128, 2>(q2, st); break;
-                default: rc = launch_attn_mfma<256, 2>(q2, st); break;
-            }
-            T.end(8 * l + 2);
+            if (split) { rc = point_scores(p1, sb + 10, sb + 11); if (rc) return rc; q2.gscore = p2; }
+            rc = T.traced(8 * l + 2, [&] {
+                return dispatch_width(dd, [&](auto w) { return launch_attn<decltype(w)::value, 2>(q2, st, epi16); });
+            });
             if (rc) return rc;
-            // pool2.mlp: SharedMLP(d, d) lrelu 0.2, then lrelu_0.01(mlp2(p2) + shortcut(feat)) as ONE linear over
-            // [p2 | feat] (randlanet.py:639, 692).  With enough rows to fill the chip the two run back to back in
-            // one launch (p2 stays in LDS); small levels keep two launches so the column passes spread over CUs.
-            ChainArgs ch = {};
-            ch.a0 = agg; ch.c0 = dd; ch.n_layers = 2;
-            ch.L[0].wt = P(sb + 12); ch.L[0].bias = P(sb + 13); ch.L[0].cin = dd; ch.L[0].cout = dd;
-            ch.L[0].act = 1; ch.L[0].slope = 0.2f;
-            ch.cat = feat; ch.cat_c = d_in; ch.cat_layer = 1;
-            ch.L[1].wt = P(sb + 14); ch.L[1].bias = P(sb + 16); ch.L[1].bias2 = P(sb + 17);
-            ch.L[1].cin = dd + d_in; ch.L[1].cout = 2 * dd; ch.L[1].act = 1; ch.L[1].slope = 0.01f;
-            ch.out = enc; ch.m_total = M;
-            // (fused when the shape has a compiled per-wave instance: the first two encoder layers of every reference
-            //  config; wide layers run faster as two tile GEMMs than through any chain kernel: 0.69 -> 0.35 ms at 128 channels)
-            if (epi16) {
-                // (done inside stage 2)
-            } else if (!no_fuse && M >= fuse_rows && chain_compiled(ch)) {
-                T.begin(8 * l + 5); rc = launch_chain_auto(ch, st); T.end(8 * l + 5); if (rc) return rc;
-            } else {
-                {
-                    LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-                    a.a0 = agg; a.c0 = dd; a.wt = P(sb + 12); a.bias = P(sb + 13); a.out = p2;
-                    a.m_total = M; a.cout = dd; a.act = 1; a.slope = 0.2f;
-                    T.begin(8 * l + 5); rc = launch_linear_auto(a, st); T.end(8 * l + 5); if (rc) return rc;
-                }
-                {
-                    LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-                    a.a0 = p2; a.c0 = dd; a.a1 = feat; a.c1 = d_in; a.wt = P(sb + 14);
-                    a.bias = P(sb + 16); a.bias2 = P(sb + 17); a.out = enc;
-                    a.m_total = M; a.cout = 2 * dd; a.act = 1; a.slope = 0.01f;
-                    T.begin(8 * l + 6); rc = launch_linear_auto(a, st); T.end(8 * l + 6); if (rc) return rc;
-                }
+            if (!epi16) {   // (epi16: done inside stage 2)
+                // pool2.mlp: SharedMLP(d, d) lrelu 0.2, then lrelu_0.01(mlp2(p2) + shortcut(feat)) as ONE linear over
+                // [p2 | feat] (randlanet.py:639, 692).  With enough rows to fill the chip the two run back to back in
+                // one launch (p2 stays in LDS); small levels keep two launches so the column passes spread over CUs.
+                // (fused when the shape has a compiled per-wave instance: the first two encoder layers of every reference
+                //  config; wide layers run faster as two tile GEMMs than through any chain kernel: 0.69 -> 0.35 ms at 128 channels)
+                const LinArgs pool2[2] = {lin(agg, dd, sb + 12, sb + 13, p2, M, dd, 0.2f),
+                                          lin(p2, dd, sb + 14, sb + 16, enc, M, 2 * dd, 0.01f, feat, d_in, sb + 17)};
+                rc = launch_linears(pool2, 2, M >= fuse_rows(), T, 8 * l + 5, st);
             }
         } else {
-            switch (dd) {
-                case 8: rc = launch_lfa<8>(s1, s2, st, trace, 8 * l + 1); break;
-                case 16: rc = launch_lfa<16>(s1, s2, st, trace, 8 * l + 1); break;
-                case 32: rc = launch_lfa<32>(s1, s2, st, trace, 8 * l + 1); break;
-                case 64: rc = launch_lfa<64>(s1, s2, st, trace, 8 * l + 1); break;
-                case 128: rc = launch_lfa<128>(s1, s2, st, trace, 8 * l + 1); break;
-                case 256: rc = launch_lfa<256>(s1, s2, st, trace, 8 * l + 1); break;
-                case 512: rc = launch_lfa<512>(s1, s2, st, trace, 8 * l + 1); break;
-                default: return ML3D_E_UNSUPPORTED;
-            }
+            rc = dispatch_width(dd, [&](auto w) { return launch_lfa<decltype(w)::value>(s1, s2, st, T, 8 * l + 1); });
         }
         if (rc) return rc;
-        {   // random_sample onto the kept prefix      (randlanet.py:278)
-            int64_t items = B * n[l + 1] * 2 * dd;
-            T.begin(8 * l + 3);
+        // random_sample onto the kept prefix      (randlanet.py:278)
+        rc = T.traced(8 * l + 3, [&] {
             const int c2 = 2 * dd;
-            if ((c2 & 3) == 0 && c2 / 4 <= 256 && n[l] * c2 < ((int64_t)1 << 32) && B < 65536 && !force_valu) {
+            if ((c2 & 3) == 0 && c2 / 4 <= 256 && n[l] * c2 < ((int64_t)1 << 32) && B < 65536) {
                 const uint32_t cv = (uint32_t)(c2 / 4), rpb = 256u / cv;
                 // (the kept points of level l are level l+1: its grid's order is their spatial order)
                 const int32_t* ord = (tile_order && l + 1 < Lr) ? tile_order[l + 1] : nullptr;
                 hipLaunchKernelGGL(gather_max4, dim3((unsigned)((n[l + 1] + rpb - 1) / rpb), (unsigned)B), dim3(256), 0, st, enc,
                                    neighbor_idx[l], samp, (uint32_t)n[l], (uint32_t)n[l + 1], cv, rpb, ord);
             } else {
+                const int64_t items = B * n[l + 1] * c2;
                 hipLaunchKernelGGL(gather_max, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, enc,
-                                   neighbor_idx[l], samp, n[l], n[l + 1], B, 2 * dd);
+                                   neighbor_idx[l], samp, n[l], n[l + 1], B, c2);
             }
-            T.end(8 * l + 3);
-            if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-        }
+            return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+        });
+        if (rc) return rc;
         if (l == 0) enc_keep[0] = enc;
         enc_keep[l + 1] = samp;
         feat = samp;
@@ -3225,13 +3198,16 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
     int slot = 2 + 18 * Lr;
     const int Dm = d_in;
     float* cur = take(B * n[Lr] * Dm);
-    {   // mlp: SharedMLP(D, D) lrelu 0.2               (randlanet.py:285)
-        LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-        a.a0 = feat; a.c0 = Dm; a.wt = P(slot); a.bias = P(slot + 1); a.out = cur;
-        a.m_total = B * n[Lr]; a.cout = Dm; a.act = 1; a.slope = 0.2f;
-        T.begin(1001); int rc = launch_linear_auto(a, st); T.end(1001); if (rc) return rc;
-        slot += 2;
-    }
+    // mlp: SharedMLP(D, D) lrelu 0.2               (randlanet.py:285)
+    rc = run(1001, lin(feat, Dm, slot, slot + 1, cur, B * n[Lr], Dm, 0.2f));
+    if (rc) return rc;
+    slot += 2;
+    // fc1 (randlanet.py:93-96, 296) behind the decoder's slots: in [B n0, k] -> 64 -> 32 -> classes, through t0 and t1
+    auto fc1 = [&, fs = slot + 2 * Lr](LinArgs* g, const float* in, int k, float* t0, float* t1) {
+        g[0] = lin(in, k, fs, fs + 1, t0, B * n[0], 64, 0.2f);
+        g[1] = lin(t0, 64, fs + 2, fs + 3, t1, B * n[0], 32, 0.2f);
+        g[2] = lin(t1, 32, fs + 4, fs + 5, out_scores, B * n[0], d->num_classes, 0.f);
+    };
     int ed[ML3D_RANDLA_MAX_LAYERS + 1];
     enc_dims(d, ed);
     int cprev = Dm;
@@ -3240,80 +3216,48 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
         const int lev = Lr - 1 - i;                 // output level
         const int skip_c = ed[Lr + 1 - i - 2];
         float* outp = take(B * n[lev] * skip_c);
-        LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-        a.a0 = enc_keep[Lr + 1 - i - 2]; a.c0 = skip_c;
-        a.a1 = cur; a.c1 = cprev; a.gather = interp_idx[lev];
-        a.rows_per_item = n[lev]; a.a1_rows_per_item = n[lev + 1];
-        a.wt = P(slot); a.bias = P(slot + 1); a.out = outp;
-        a.m_total = B * n[lev]; a.cout = skip_c; a.act = 1; a.slope = 0.2f;
-        if (i == Lr - 1 && !no_fuse && !force_valu) {
+        LinArgs a = lin(enc_keep[Lr + 1 - i - 2], skip_c, slot, slot + 1, outp, B * n[lev], skip_c, 0.2f, cur, cprev);
+        a.gather = interp_idx[lev]; a.rows_per_item = n[lev]; a.a1_rows_per_item = n[lev + 1];
+        if (i == Lr - 1) {
             // the last decoder stage feeds only fc1: run [skip | interp] -> decoder -> fc1.0 -> fc1.1 -> fc1.3 as ONE
-            // per-wave chain when the shape has a compiled instance (the N0 x 32 decoder output never exists in HBM)
-            ChainArgs ch = {};
-            ch.a0 = a.a0; ch.c0 = a.c0; ch.a1 = a.a1; ch.c1 = a.c1; ch.gather = a.gather;
-            ch.rows_per_item = a.rows_per_item; ch.a1_rows_per_item = a.a1_rows_per_item;
-            ch.n_layers = 4;
-            ch.L[0].wt = a.wt; ch.L[0].bias = a.bias; ch.L[0].cin = a.c0 + a.c1; ch.L[0].cout = skip_c; ch.L[0].act = 1; ch.L[0].slope = 0.2f;
-            ch.L[1].wt = P(slot + 2); ch.L[1].bias = P(slot + 3); ch.L[1].cin = skip_c; ch.L[1].cout = 64; ch.L[1].act = 1; ch.L[1].slope = 0.2f;
-            ch.L[2].wt = P(slot + 4); ch.L[2].bias = P(slot + 5); ch.L[2].cin = 64; ch.L[2].cout = 32; ch.L[2].act = 1; ch.L[2].slope = 0.2f;
-            ch.L[3].wt = P(slot + 6); ch.L[3].bias = P(slot + 7); ch.L[3].cin = 32; ch.L[3].cout = d->num_classes; ch.L[3].act = 0;
-            ch.out = out_scores; ch.m_total = a.m_total;
-            const bool dec_fuse = knobs().dec_fc1;
-            if (dec_fuse && knobs().mlp_shaped && mlp_shape_matches<ShapeDecFc1>(ch)) {
-                T.begin(1200); int rc = launch_chain_auto(ch, st); T.end(1200);
-                return rc;
-            }
+            // per-wave chain when the shape has a compiled instance (the N0 x 32 decoder output never exists in HBM,
+            // nor do fc1's intermediates)
+            LinArgs g[4] = {a};
+            fc1(g + 1, outp, skip_c, nullptr, nullptr);
+            const ChainArgs ch = chain_of(g, 4);
+            if (mlp_shape_matches<ShapeDecFc1>(ch)) return T.traced(1200, [&] { return launch_chain_auto(ch, st); });
         }
         // W . [skip ; up[idx]] = W_skip . skip + (W_up . up)[idx]: the upsampled half is linear in a per-COARSE-point
         // quantity, computed once per coarse point (1/ratio of the rows) and added back through the interpolation index
         // as a gathered residual of the skip GEMM
-        const bool dec_split = knobs().dec_split;
-        if (dec_split && !force_valu && n[lev] >= 64 && (skip_c & 3) == 0 && (cprev & 3) == 0 && skip_c >= 8) {
+        if (n[lev] >= 64 && (skip_c & 3) == 0 && (cprev & 3) == 0 && skip_c >= 8) {
             float* up = take(B * n[lev + 1] * skip_c);
-            RowsA Au = {};
-            Au.a = cur; Au.lda = cprev; Au.k1 = cprev;
-            T.begin(1100 + i);
-            int rc = gemm_rows(Au, a.wt + (int64_t)skip_c * skip_c, B * n[lev + 1], skip_c, cprev, Epilogue{}, up, skip_c, nullptr, 0, st);
-            if (rc) return rc;
-            RowsA As = {};
-            As.a = a.a0; As.lda = skip_c; As.k1 = skip_c;
-            // (the interpolation index is item-local: n[lev] rows per item here, n[lev + 1] coarse rows per item in `up`)
-            const Epilogue e1 = Epilogue::of(a.bias, 1, 0.2f).residual_rows(up, skip_c).gathered_residual(a.gather, 0, n[lev + 1], n[lev], n[lev + 1]);
-            rc = gemm_rows(As, a.wt, a.m_total, skip_c, skip_c, e1, outp, skip_c, nullptr, 0, st);
-            T.end(1100 + i);
-            if (rc) return rc;
+            rc = T.traced(1100 + i, [&] {
+                RowsA Au = {};
+                Au.a = cur; Au.lda = cprev; Au.k1 = cprev;
+                const int r = gemm_rows(Au, a.wt + (int64_t)skip_c * skip_c, B * n[lev + 1], skip_c, cprev, Epilogue{}, up, skip_c, nullptr, 0, st);
+                if (r) return r;
+                RowsA As = {};
+                As.a = a.a0; As.lda = skip_c; As.k1 = skip_c;
+                // (the interpolation index is item-local: n[lev] rows per item here, n[lev + 1] coarse rows per item in `up`)
+                const Epilogue e1 = Epilogue::of(a.bias, 1, 0.2f).residual_rows(up, skip_c).gathered_residual(a.gather, 0, n[lev + 1], n[lev], n[lev + 1]);
+                return gemm_rows(As, a.wt, a.m_total, skip_c, skip_c, e1, outp, skip_c, nullptr, 0, st);
+            });
         } else {
-            T.begin(1100 + i); int rc = launch_linear_auto(a, st); T.end(1100 + i); if (rc) return rc;
+            rc = run(1100 + i, a);
         }
+        if (rc) return rc;
         slot += 2;
         cur = outp;
         cprev = skip_c;
     }
     float* t0 = take(B * n[0] * 64);
     float* t1 = take(B * n[0] * 32);
-    {   // fc1                                            (randlanet.py:93-96, 296)
-        LinArgs a = {}; a.pack_ws = pack_ws; a.pack_bytes = pack_bytes;
-        a.a0 = cur; a.c0 = cprev; a.wt = P(slot); a.bias = P(slot + 1); a.out = t0;
-        a.m_total = B * n[0]; a.cout = 64; a.act = 1; a.slope = 0.2f;
-        ChainArgs ch = {};
-        ch.a0 = cur; ch.c0 = cprev; ch.n_layers = 3;
-        ch.L[0].wt = P(slot); ch.L[0].bias = P(slot + 1); ch.L[0].cin = cprev; ch.L[0].cout = 64; ch.L[0].act = 1; ch.L[0].slope = 0.2f;
-        ch.L[1].wt = P(slot + 2); ch.L[1].bias = P(slot + 3); ch.L[1].cin = 64; ch.L[1].cout = 32; ch.L[1].act = 1; ch.L[1].slope = 0.2f;
-        ch.L[2].wt = P(slot + 4); ch.L[2].bias = P(slot + 5); ch.L[2].cin = 32; ch.L[2].cout = d->num_classes; ch.L[2].act = 0;
-        ch.out = out_scores; ch.m_total = B * n[0];
-        if (!no_fuse && !force_valu && chain_compiled(ch)) {
-            // fc1.0 -> fc1.1 -> fc1.3 back to back: the 64- and 32-wide activations never leave LDS
-            T.begin(1200); int rc = launch_chain_auto(ch, st); T.end(1200); if (rc) return rc;
-        } else {
-            T.begin(1200); int rc = launch_linear_auto(a, st); T.end(1200); if (rc) return rc;
-            a.a0 = t0; a.c0 = 64; a.wt = P(slot + 2); a.bias = P(slot + 3); a.out = t1; a.cout = 32;
-            T.begin(1201); rc = launch_linear_auto(a, st); T.end(1201); if (rc) return rc;
-            a.a0 = t1; a.c0 = 32; a.wt = P(slot + 4); a.bias = P(slot + 5); a.out = out_scores;
-            a.cout = d->num_classes; a.act = 0;
-            T.begin(1202); rc = launch_linear_auto(a, st); T.end(1202); if (rc) return rc;
-        }
-    }
-    return 0;
+    // fc1.0 -> fc1.1 -> fc1.3 back to back where the shape has a compiled chain (the 64- and 32-wide activations never leave
+    // LDS), one launch per layer otherwise
+    LinArgs g[3];
+    fc1(g, cur, cprev, t0, t1);
+    return launch_linears(g, 3, true, T, 1200, st);
 }
 
 // ---- random_sample as a stand-alone differentiable op (training side) ------------------------------------

@@ -132,8 +132,8 @@ print("VARIANT_OK", err)
 
 
 def _run_variant(knobs, ci, B, N, seed_pts, seed_w):
-    """The library reads its ML3D_* A/B switches once per process (randla.hip: knobs()), so every setting gets its own
-    interpreter."""
+    """The emulator build reads its one test hook, ML3D_RANDLA_FUSE_ROWS, once per process (randla.hip: fuse_rows()), so every
+    setting gets its own interpreter."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
