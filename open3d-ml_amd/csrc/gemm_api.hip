@@ -23,6 +23,8 @@ extern "C" size_t ml3d_linear_bf16x3_workspace_bytes(int64_t rows, int n, int k)
 extern "C" int ml3d_linear_bf16x3(const float* a, int64_t lda, int k1, const float* a2, int64_t lda2, int k2, int64_t rows,
                                   const void* packed, const float* bias, const float* residual, int64_t ldr, int n, int act,
                                   float slope, float* out, int64_t ldc, void* workspace, size_t workspace_bytes, void* stream) {
+    // (zero rows is a no-op before any pointer is looked at, as in ml3d_linear: an empty tensor has no address)
+    if (rows == 0 && k1 > 0 && k2 >= 0 && n > 0 && act >= 0 && act <= 2) return 0;
     if (rows < 0 || k1 <= 0 || k2 < 0 || n <= 0 || lda < k1 || (k2 > 0 && (!a2 || lda2 < k2)) || ldc < n || !a || !packed || !out ||
         act < 0 || act > 2 || (residual && ldr < n))
         return ML3D_E_INVALID;
@@ -38,6 +40,7 @@ extern "C" int ml3d_linear_bf16x3_gathered(const float* a, int64_t lda, int k1, 
                                            const int32_t* residual_gather, int64_t residual_gather_stride, int64_t residual_rows, int n,
                                            int act, float slope, float* out, int64_t ldc, void* workspace, size_t workspace_bytes,
                                            void* stream) {
+    if (rows == 0 && k1 > 0 && k2 >= 0 && n > 0 && act >= 0 && act <= 2) return 0;
     if (rows < 0 || k1 <= 0 || k2 < 0 || n <= 0 || lda < k1 || (k2 > 0 && (!a2 || lda2 < k2)) || ldc < n || !a || !packed || !out ||
         act < 0 || act > 2 || (residual && ldr < n) || (residual_gather && (!residual || residual_gather_stride < 1 || residual_rows < 0)))
         return ML3D_E_INVALID;
