@@ -11,10 +11,18 @@
 // to HBM.
 //
 // Kernels
-//   linear_act      y = act(b + [a0 | a1[gather]] . WT)        (fc0, mlp1, mlp, decoder, fc1)
-//   lfa_stage<1>    LocalSpatialEncoding #1 + AttentivePooling #1   -> p1 [N, d/2]
-//   lfa_stage<2>    LSE #2 + AttentivePooling #2 + mlp2 + shortcut  -> enc [N, 2d]
-//   gather_max      random_sample: max over the K neighbours of the kept prefix
+//   head_fc0_mlp1      fc0 + the first layer's mlp1 in one pass over the input rows
+//   linear_act         y = act(b + [a0 | a1[gather]] . WT): the generic per-point Linear
+//   lfa_stage<D, 1|2>  one LocalFeatureAggregation stage on the VALU, any width: the fallback of the MFMA kernels below
+//   the attention part of a stage (position encoding, scores, softmax over K, weighted sum -> agg [N, D]) on the matrix pipe:
+//     lfa_attn_mfma16    D = 16, f32 MFMA, optionally with the per-point Linears behind the stage (EPI)
+//     lfa_attn_wave      D = 32, 64, f32 MFMA, one wave per 2-point tile
+//     lfa_attn_wave_b3   D = 64, the same on the bf16 pipe (three-way split)
+//     lfa_attn_pf        D = 128, 256, f32 MFMA, one workgroup per tile
+//     lfa_attn_b3        D = 128, 256, the same on the bf16 pipe
+//   mlp_wave_s, mlp_chain_b3   chains of per-point Linears with the activations on chip (f32 MFMA / bf16 pipe)
+//   gather_max, gather_max4    random_sample: max over the K neighbours of the kept prefix
+//   gather_max_adjoint, attentive_pool_k   the training ops' backward / differentiable forms
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -468,24 +476,22 @@ static int launch_attn_tiles(Kern kern, LfaArgs a, int64_t tiles, int tiles_per_
 
 #define SYNC_ATTN() block_sync_lds()   // LDS-only workgroup barrier (grid.h): global loads / stores stay in flight
 
+// lfa_attn_pf's tile shape (D = 128, 256: the narrower widths run on the per-wave kernels)
 template <int D>
 struct MfmaCfg {
+    static_assert(D >= 128, "lfa_attn_pf: D in {128, 256}");
     static constexpr int H = D / 2;
     static constexpr int NT = D / 32;                        // score column tiles
-    static constexpr int NT2 = (H + 31) / 32;                // lse2 column tiles
+    static constexpr int NT2 = H / 32;                       // lse2 column tiles
     static constexpr int WAVES = NT > 4 ? NT : 4;
     static constexpr int THREADS = WAVES * 64;
-    static constexpr int TP = D <= 64 ? 8 : (D == 128 ? 4 : 2);   // points per tile (half-size tiles measured slower)
+    static constexpr int TP = D == 128 ? 4 : 2;              // points per tile (half-size tiles measured slower)
     static constexpr int ROWS = TP * RK;
     static constexpr int RT = ROWS / 32;                     // 32-row MFMA tiles
     static constexpr int RG = WAVES / NT;                    // waves sharing a column tile take different row tiles
     static constexpr int RG2 = WAVES / NT2;
     static constexpr int XP = D + 4;                         // LDS row pitch of X
     static constexpr int RP = H + 4;                         // LDS row pitch of R1
-    // H <= 32: one wave owns all H columns of its row tile, so lse2 can run IN PLACE on X[:, H:] (its A operand is
-    // in registers before its result is stored) and the separate R1 tile (ROWS x RP floats of LDS) disappears:
-    // 60 -> 41 KB per workgroup at D = 64, i.e. three resident workgroups per CU instead of two
-    static constexpr bool INPLACE = NT2 == 1;
 };
 
 __device__ __forceinline__ int mfma_row(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
@@ -538,95 +544,72 @@ __device__ __forceinline__ void softmax_wsum8(const ACC& sc, int o /* 0 or 8 */,
 }
 
 // ------------------------------------------------------------------------------------------------
-// lfa_attn_pf — the same attention stage with the NEXT tile's global traffic in flight under the
-// current tile's MFMA phases.  A tile needs three dependent global hops (neighbour index -> neighbour
-// xyz / neighbour feature row); in lfa_attn_mfma every workgroup sits through them at the top of each
-// tile (~3.5 us of a ~12 us tile).  Here each thread owns, across tiles, the same slots of the tile's
-// inputs: G float4 pieces of the gathered feature rows and (threads < ROWS) one (point, neighbour) row of
-// relative positions.  Schedule per tile t:
-//     registers -> LDS: X[:, 0:H] <- feature pieces, REL <- relative positions          (loads of t landed)
-//     request the neighbour indices of t+1                                             (hop 1)
-//     barrier; lse1 [; lse2]                                                           (MFMA)
-//     request xyz + feature pieces of t+1 through those indices                        (hops 2, 3)
-//     barrier; scores, softmax, weighted sum (the long MFMA phase); barrier
-// The barriers are block_sync_lds (LDS only), so the requests stay in flight across them.  lse1/lse2
-// weights move from registers to LDS (B operand by ds_read) to make room for the in-flight registers,
-// and with lse2 in place (H <= 32) the lse1 -> lse2 hand-off is inside one wave: 3 barriers per tile.
+// What the MFMA attention kernels share: the tile walk, the prefetch of the next tile's inputs (one form per
+// workgroup-tile kernel, one per per-wave kernel), the relative-position row and the gscore gather.
 // ------------------------------------------------------------------------------------------------
-// SPLIT: the score Linear acts on X = [gathered neighbour features | encoded positions], and its first half is linear
-// in a PER-POINT quantity: W . [f[nb] ; r] = (W_top . f)[nb] + W_bot . r.  With A.gscore = f . W_top^T precomputed
-// per point by one small GEMM (1/16 of the work it replaces), the kernel gathers the neighbour's gscore row straight
-// into the accumulator layout (32 lanes read 128 contiguous bytes of a row) and runs the MFMAs over K = H instead
-// of D: half the score MFMAs and half the resident weight registers.  f[nb] is still gathered into X for the
-// weighted sum.  Used for D >= 128, where the extra D floats per neighbour are small next to the MFMA time saved.
-template <int D, int STAGE, bool SPLIT, bool ORD>
-__global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (D <= 64 ? 3 : (MfmaCfg<D>::THREADS / 256))) lfa_attn_pf(LfaArgs A) {
-    using C = MfmaCfg<D>;
-    constexpr int H = C::H, ROWS = C::ROWS, XP = C::XP, RP = C::RP, THREADS = C::THREADS;
-    constexpr int HP = C::NT2 * 32;                               // lse weight pitch (column tiles, zero padded)
-    constexpr int Q = H / 4;                                      // float4 pieces per gathered row
-    constexpr int G = ROWS * Q / THREADS;                         // pieces per thread
-    static_assert(ROWS * Q % THREADS == 0 && ROWS <= THREADS, "tile shape");
-    HIP_DYNAMIC_SHARED(float, smem)
-    float* X = smem;                                              // [ROWS][XP]
-    float* R1 = X + ROWS * XP;                                    // [ROWS][RP]   (stage 2, unless in place)
-    float* REL = R1 + ((STAGE == 2 && !C::INPLACE) ? ROWS * RP : 0);   // [ROWS][12]
-    float* W1 = REL + ROWS * 12;                                  // [12][HP]
-    float* W2 = W1 + 12 * HP;                                     // [H][HP]      (stage 2)
-    uint32_t* NROWG = reinterpret_cast<uint32_t*>(W2 + (STAGE == 2 ? H * HP : 0));   // [ROWS] global neighbour row (SPLIT)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hi = lane >> 5, col = lane & 31;
-
-    const int ct = wave % C::NT, rg = wave / C::NT;
-    constexpr int KS = SPLIT ? H : D, K0 = SPLIT ? H : 0;         // score MFMAs run over input channels [K0, K0 + KS)
-    float bs[KS / 2];
-#pragma unroll
-    for (int s = 0; s < KS / 2; ++s) bs[s] = A.score_wt[(K0 + hi * (KS / 2) + s) * D + ct * 32 + col];
-    const float sbias = A.score_b[ct * 32 + col];
-    const int ct2 = wave % C::NT2, rg2 = wave / C::NT2;
-    const int col2 = ct2 * 32 + col;
-    for (int e = tid; e < 12 * HP; e += THREADS) {
-        const int k = e / HP, c = e - k * HP;
-        W1[e] = (k < 10 && c < H) ? A.lse1_wt[k * H + c] : 0.f;
-    }
-    float l2bias = 0.f;
-    if constexpr (STAGE == 2) {
-        for (int e = tid; e < H * HP; e += THREADS) {
-            const int k = e / HP, c = e - k * HP;
-            W2[e] = c < H ? A.lse2_wt[k * H + c] : 0.f;
-        }
-        l2bias = col2 < H ? A.lse2_b[col2] : 0.f;
-    }
-    const float b1 = col2 < H ? A.lse1_b[col2] : 0.f;
-
-    const int64_t tiles = (A.m_total + C::TP - 1) / C::TP;
-    const bool xw = A.xcd_chunk > 0;
-    const int64_t w_step = xw ? (int64_t)(gridDim.x >> 3) : (int64_t)gridDim.x;
-    int64_t wi = xw ? (int64_t)(blockIdx.x >> 3) : (int64_t)blockIdx.x;
-    auto next_tile = [&]() -> int64_t {
+// The tiles of one worker slot (a workgroup, or one wave of a workgroup), in turn: slot `slot` of `slots` per workgroup
+// takes tiles index, index + stride, .. of the grid's walk, through xcd_tile when the launcher cut the tiles into chunks.
+// I: the width of the bookkeeping (uint32_t where it must stay in a few SGPRs; see lfa_attn_wave).
+template <class I>
+struct TileWalk {
+    const int64_t chunk, tiles;
+    const bool xw;
+    const I step;
+    I wi;
+    __device__ __forceinline__ TileWalk(int64_t xcd_chunk, I n_tiles, I slots, I slot)
+        : chunk(xcd_chunk), tiles((int64_t)n_tiles), xw(xcd_chunk > 0),
+          step((I)(xw ? (gridDim.x >> 3) : gridDim.x) * slots), wi((I)(xw ? (blockIdx.x >> 3) : blockIdx.x) * slots + slot) {}
+    // the slot's next tile, or -1 when it has none left
+    __device__ __forceinline__ int64_t next() {
         for (;;) {
-            int64_t t = wi;
-            if (xw) t = xcd_tile(wi, (int)(blockIdx.x & 7), A.xcd_chunk, tiles);
-            wi += w_step;
+            int64_t t = (int64_t)wi;
+            if (xw) t = xcd_tile((int64_t)wi, (int)(blockIdx.x & 7), chunk, tiles);
+            wi += step;
             if (t < 0) return -1;
             if (t < tiles) return t;
             if (!xw) return -1;
         }
-    };
+    }
+};
 
-    // ---- this thread's slots of a tile's inputs ---------------------------------------------------
+// one (point, neighbour) row of the lse1 input (randlanet.py:579-594): |q - s|, q - s, q, s; zeros for a row past the end of
+// the data.  K slot 10 is `k10` (1: the slot that carries lse1's bias as a weight row), slot 11 the K padding of the MFMA.
+__device__ __forceinline__ void rel_row(float* r, bool valid, float qx, float qy, float qz, float sx, float sy, float sz, float k10) {
+    if (valid) {
+        const float dx = qx - sx, dy = qy - sy, dz = qz - sz;
+        r[0] = sqrtf(dx * dx + dy * dy + dz * dz);
+        r[1] = dx; r[2] = dy; r[3] = dz; r[4] = qx; r[5] = qy; r[6] = qz; r[7] = sx; r[8] = sy; r[9] = sz;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 10; ++j) r[j] = 0.f;
+    }
+    r[10] = k10; r[11] = 0.f;
+}
+
+// ---- the prefetch of the workgroup-tile kernels (lfa_attn_pf, lfa_attn_b3) ------------------------------------------------
+// Each thread owns, across tiles, the same slots of a tile's inputs: G float4 pieces of the gathered feature rows and
+// (threads < ROWS) one (point, neighbour) row of relative positions.  request_idx(t + 1) and request_data(t + 1) are issued
+// under the MFMA phases of tile t, to_lds() moves what landed into the tile's LDS at the top of t + 1.
+// C: the kernel's Cfg (TP, ROWS, THREADS); RELP: float pitch of REL; BIAS_SLOT: K slot 10 of a REL row is 1 (lse1's bias is a
+// weight row) instead of 0; GROW: the byte offset of each row's gscore row goes to NROWG.
+// (per-tile bookkeeping is wave-uniform and 32-bit: f32 MFMA and VALU share the SIMD's issue cycles on gfx950, so a
+//  64-bit division per lane per tile costs as much as two MFMAs; the launcher guarantees m_total, n0 < 2^30, n >= TP.
+//  The arrays are indexed under full unrolling only: everything here lives in registers.)
+template <class C, int D, bool ORD, int RELP, bool BIAS_SLOT, bool GROW>
+struct TilePrefetch {
+    static constexpr int H = D / 2, ROWS = C::ROWS, THREADS = C::THREADS;
+    static constexpr int Q = H / 4;                               // float4 pieces per gathered row
+    static constexpr int G = ROWS * Q / THREADS;                  // pieces per thread
+    static_assert(ROWS * Q % THREADS == 0 && ROWS <= THREADS, "tile shape");
     int gi[G], nb_mine = 0;              // hop 1: neighbour rows (item-local)
     float4 gq[G];                        // hop 3: gathered feature pieces
     float qx = 0.f, qy = 0.f, qz = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;   // hop 2
     bool mine_valid = false;
-    uint32_t grow_mine = 0;              // global row of this thread's neighbour (SPLIT)
-    // (per-tile bookkeeping is wave-uniform and 32-bit: f32 MFMA and VALU share the SIMD's issue cycles on gfx950, so a
-    //  64-bit division per lane per tile costs as much as two MFMAs; the launcher guarantees m_total, n0 < 2^30, n >= TP)
-    const uint32_t n_pts = (uint32_t)A.n, m_tot = (uint32_t)A.m_total;
+    uint32_t grow_mine = 0;              // global row of this thread's neighbour (GROW)
     uint32_t gmp[ORD ? G : 1], mp_mine = 0, m_first = 0;     // ORD: point rows of this thread's slots / of the tile's first point
-    auto request_idx = [&](uint32_t tile) {
-        const uint32_t have = m_tot - tile * C::TP;                 // points of the tile that exist
+
+    __device__ __forceinline__ void request_idx(const LfaArgs& A, int tid, uint32_t tile) {
+        const uint32_t have = (uint32_t)A.m_total - tile * C::TP;   // points of the tile that exist
         const uint32_t lim = (have < (uint32_t)C::TP ? have : (uint32_t)C::TP) * RK;
         if constexpr (ORD) {
             const int32_t* ord = A.order + tile * C::TP;
@@ -656,10 +639,12 @@ __global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (D <= 64 ? 3 : (MfmaCfg
             }
             if (tid < ROWS) nb_mine = (uint32_t)tid < lim ? nb[tid] : -1;
         }
-    };
-    auto request_data = [&](uint32_t tile) {
+    }
+
+    __device__ __forceinline__ void request_data(const LfaArgs& A, int tid, uint32_t tile) {
         // scalar: the cloud of the tile's first point; the tile's other points are in it or in the next one (ORD: the
         // order is cloud-major, so the same holds for order[t * TP ..])
+        const uint32_t n_pts = (uint32_t)A.n;
         const uint32_t m0 = ORD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)m_first) : tile * C::TP;
         const uint32_t b0 = m0 / n_pts, l0 = m0 - b0 * n_pts;
 #pragma unroll
@@ -694,39 +679,224 @@ __global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (D <= 64 ? 3 : (MfmaCfg
                 qx = qp[0]; qy = qp[1]; qz = qp[2]; sx = sp[0]; sy = sp[1]; sz = sp[2];
             }
         }
-    };
+    }
 
-    int64_t cur = next_tile();
-    if (cur >= 0) { request_idx((uint32_t)cur); request_data((uint32_t)cur); }
-    block_sync_lds();                                            // W1 / W2 staged
-    while (cur >= 0) {
-        const int64_t nxt = next_tile();
-        const int64_t m_base = cur * C::TP;
-        // ---- registers -> LDS -----------------------------------------------------------------------
+    // registers -> LDS: X[:, 0:H] <- feature pieces (pitch D + 4), REL <- relative positions, NROWG <- gscore row offsets
+    __device__ __forceinline__ void to_lds(int tid, float* X, float* REL, uint32_t* NROWG) const {
 #pragma unroll
         for (int i = 0; i < G; ++i) {
             const int e = tid + i * THREADS;
             const int row = e / Q, q = e - row * Q;
-            *reinterpret_cast<float4*>(X + row * XP + 4 * q) = gq[i];
+            *reinterpret_cast<float4*>(X + row * (D + 4) + 4 * q) = gq[i];
         }
         if (tid < ROWS) {
-            float* r = REL + tid * 12;
-            if (mine_valid) {
-                const float dx = qx - sx, dy = qy - sy, dz = qz - sz;
-                r[0] = sqrtf(dx * dx + dy * dy + dz * dz);
-                r[1] = dx; r[2] = dy; r[3] = dz; r[4] = qx; r[5] = qy; r[6] = qz; r[7] = sx; r[8] = sy; r[9] = sz;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 10; ++j) r[j] = 0.f;
-            }
-            r[10] = 0.f; r[11] = 0.f;                              // K padding of the lse1 MFMA
+            rel_row(REL + tid * RELP, mine_valid, qx, qy, qz, sx, sy, sz, BIAS_SLOT ? 1.f : 0.f);
             // byte offset of the neighbour's gscore row (the launcher keeps m * D * 4 below 2^32); rows past the end of
             // the data read row 0 -- their scores feed outputs that are never stored
-            if constexpr (SPLIT) NROWG[tid] = mine_valid ? grow_mine * (uint32_t)(D * 4) : 0u;
+            if constexpr (GROW) NROWG[tid] = mine_valid ? grow_mine * (uint32_t)(D * 4) : 0u;
         }
-        if (nxt >= 0) request_idx((uint32_t)nxt);
+    }
+};
+
+// the neighbours' gscore rows (A.gscore, one row per POINT) -> the score accumulator of one 32-row tile, through the rows' byte
+// offsets in LDS (nrowg: the tile's 32 offsets; gscore_ct: the wave's 32-column tile of the rows, a wave-uniform base)
+template <class ACC>
+__device__ __forceinline__ void gscore_gather_tile(const float* gscore_ct, const uint32_t* nrowg, int hi, int col, ACC& acc) {
+    const char* gbase = reinterpret_cast<const char*>(gscore_ct);
+    const uint32_t col4 = 4u * col;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const uint4 nr = *reinterpret_cast<const uint4*>(nrowg + 8 * q4 + 4 * hi);   // rows mfma_row(4 q4 .. 4 q4 + 3)
+        acc[4 * q4 + 0] = *reinterpret_cast<const float*>(gbase + (nr.x + col4));
+        acc[4 * q4 + 1] = *reinterpret_cast<const float*>(gbase + (nr.y + col4));
+        acc[4 * q4 + 2] = *reinterpret_cast<const float*>(gbase + (nr.z + col4));
+        acc[4 * q4 + 3] = *reinterpret_cast<const float*>(gbase + (nr.w + col4));
+    }
+}
+
+// ---- the prefetch of the per-wave kernels (lfa_attn_wave, lfa_attn_wave_b3) ------------------------------------------------
+// A wave owns whole 32-row tiles (2 points x 16 neighbours): each lane holds G float4 pieces of the gathered feature rows and
+// (lanes < 32) one (point, neighbour) row of relative positions, requested one tile ahead as in TilePrefetch.  The streaming
+// neighbour indices go around the L2's LRU (non-temporal).  GOFF: the byte offset of each row's gscore row goes to the patch.
+template <int D, bool ORD, bool GOFF>
+struct WavePrefetch {
+    static constexpr int H = D / 2;
+    static constexpr int Q = H / 4;                  // float4 pieces per gathered row
+    static constexpr int G = 32 * Q / 64;            // pieces per lane
+    static_assert((32 * Q) % 64 == 0, "tile shape");
+    int gi[G], nb_mine = -1;
+    float4 gq[G];
+    float qx = 0.f, qy = 0.f, qz = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
+    bool mine_valid = false;
+    uint32_t goff_mine = 0;
+    uint32_t mo0 = 0, mo1 = 0;           // ORD: the tile's two point rows (order[2 t], order[2 t + 1]; wave-uniform values)
+
+    __device__ __forceinline__ void request_idx(const LfaArgs& A, int lane, uint32_t tile) {
+        const uint32_t lim = ((uint32_t)A.m_total - tile * 2) >= 2 ? 32u : 16u;   // rows of the tile that exist
+        if constexpr (ORD) {
+            mo0 = (uint32_t)A.order[tile * 2];
+            mo1 = lim == 32u ? (uint32_t)A.order[tile * 2 + 1] : mo0;
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const uint32_t row = (uint32_t)(lane + 64 * i) / Q;
+                gi[i] = row < lim ? __builtin_nontemporal_load(A.nidx + (int64_t)(row < RK ? mo0 : mo1) * RK + (row & (RK - 1))) : -1;
+            }
+            nb_mine = (uint32_t)lane < lim
+                          ? __builtin_nontemporal_load(A.nidx + (int64_t)(lane < RK ? mo0 : mo1) * RK + (lane & (RK - 1))) : -1;
+        } else {
+            const int32_t* nb = A.nidx + (int64_t)tile * 2 * RK;  // 32 contiguous (point, neighbour) rows
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const uint32_t row = (uint32_t)(lane + 64 * i) / Q;
+                gi[i] = row < lim ? __builtin_nontemporal_load(nb + row) : -1;
+            }
+            nb_mine = (uint32_t)lane < lim ? __builtin_nontemporal_load(nb + lane) : -1;
+        }
+    }
+
+    __device__ __forceinline__ void request_data(const LfaArgs& A, int lane, uint32_t tile) {
+        // the tile's two points: cloud b0 / local index l0, and its successor (possibly the next cloud's first point);
+        // ORD: two arbitrary rows, each located by its own scalar division
+        const uint32_t n_pts = (uint32_t)A.n;
+        uint32_t b0, l0, b1, l1;
+        if constexpr (ORD) {
+            const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo0);
+            const uint32_t m1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo1);
+            b0 = m0 / n_pts; l0 = m0 - b0 * n_pts;
+            b1 = m1 / n_pts; l1 = m1 - b1 * n_pts;
+        } else {
+            const uint32_t m0 = tile * 2;
+            b0 = m0 / n_pts; l0 = m0 - b0 * n_pts;
+            const bool wrap = l0 + 1 == n_pts;
+            b1 = wrap ? b0 + 1 : b0; l1 = wrap ? 0u : l0 + 1;
+        }
+        const float* f0 = A.gfeat + (int64_t)b0 * n_pts * H;      // scalar bases, 32-bit lane offsets
+        const float* f1 = A.gfeat + (int64_t)b1 * n_pts * H;
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int e = lane + 64 * i;
+            const int row = e / Q, q = e - row * Q;
+            gq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (gi[i] >= 0) gq[i] = *reinterpret_cast<const float4*>((row < RK ? f0 : f1) + (uint32_t)gi[i] * H + 4 * q);
+        }
+        mine_valid = lane < 32 && nb_mine >= 0;
+        if (mine_valid) {
+            const bool p1 = lane >= RK;
+            goff_mine = ((p1 ? b1 : b0) * n_pts + (uint32_t)nb_mine) * (uint32_t)(D * 4);
+            const float* xb = A.xyz + 3 * ((int64_t)(p1 ? b1 : b0) * A.n0);
+            const float* qp = xb + 3 * (p1 ? l1 : l0);
+            const float* sp = xb + 3 * (uint32_t)nb_mine;
+            qx = qp[0]; qy = qp[1]; qz = qp[2]; sx = sp[0]; sy = sp[1]; sz = sp[2];
+        }
+    }
+
+    // registers -> the wave's patch: X[:, 0:H] (pitch D + 4), REL [32][12] with the bias slot, goff [32]
+    __device__ __forceinline__ void to_patch(int lane, float* X, float* REL, uint32_t* goff) const {
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const int e = lane + 64 * i;
+            const int row = e / Q, q = e - row * Q;
+            *reinterpret_cast<float4*>(X + row * (D + 4) + 4 * q) = gq[i];
+        }
+        if (lane < 32) {
+            rel_row(REL + lane * 12, mine_valid, qx, qy, qz, sx, sy, sz, 1.f);
+            if constexpr (GOFF) goff[lane] = mine_valid ? goff_mine : 0u;    // (rows past the data read row 0: never stored)
+        }
+    }
+};
+
+// the neighbours' gscore rows -> the score accumulators of all NT column tiles of the wave's 32-row tile (goff: its 32 offsets)
+template <int NT>
+__device__ __forceinline__ void gscore_gather_wave(const float* gscore, const uint32_t* goff, int hi, int col, f32x16 (&sc)[NT]) {
+    const char* gbase = reinterpret_cast<const char*>(gscore);
+    const uint32_t col4 = 4u * col;
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+        const uint4 go = *reinterpret_cast<const uint4*>(goff + 8 * q4 + 4 * hi);     // rows mfma_row(4 q4 .. 4 q4 + 3)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            sc[t][4 * q4 + 0] = *reinterpret_cast<const float*>(gbase + (go.x + col4 + 128u * t));
+            sc[t][4 * q4 + 1] = *reinterpret_cast<const float*>(gbase + (go.y + col4 + 128u * t));
+            sc[t][4 * q4 + 2] = *reinterpret_cast<const float*>(gbase + (go.z + col4 + 128u * t));
+            sc[t][4 * q4 + 3] = *reinterpret_cast<const float*>(gbase + (go.w + col4 + 128u * t));
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// lfa_attn_pf (D in {128, 256}) — the attention stage on the f32 MFMA with the NEXT tile's global traffic
+// in flight under the current tile's MFMA phases.  A tile needs three dependent global hops (neighbour
+// index -> neighbour xyz / neighbour feature row); a workgroup that sat through them at the top of each
+// tile lost ~3.5 us of a ~12 us tile.  Here each thread owns, across tiles, the same slots of the tile's
+// inputs (TilePrefetch).  Schedule per tile t:
+//     registers -> LDS: X[:, 0:H] <- feature pieces, REL <- relative positions          (loads of t landed)
+//     request the neighbour indices of t+1                                             (hop 1)
+//     barrier; lse1 [; lse2]                                                           (MFMA)
+//     request xyz + feature pieces of t+1 through those indices                        (hops 2, 3)
+//     barrier; scores, softmax, weighted sum (the long MFMA phase); barrier
+// The barriers are block_sync_lds (LDS only), so the requests stay in flight across them.  lse1/lse2
+// weights sit in LDS (B operand by ds_read) to make room for the in-flight registers.
+// ------------------------------------------------------------------------------------------------
+// SPLIT: the score Linear acts on X = [gathered neighbour features | encoded positions], and its first half is linear
+// in a PER-POINT quantity: W . [f[nb] ; r] = (W_top . f)[nb] + W_bot . r.  With A.gscore = f . W_top^T precomputed
+// per point by one small GEMM (1/16 of the work it replaces), the kernel gathers the neighbour's gscore row straight
+// into the accumulator layout (32 lanes read 128 contiguous bytes of a row) and runs the MFMAs over K = H instead
+// of D: half the score MFMAs and half the resident weight registers.  f[nb] is still gathered into X for the
+// weighted sum.  Used for D >= 128, where the extra D floats per neighbour are small next to the MFMA time saved.
+template <int D, int STAGE, bool SPLIT, bool ORD>
+__global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (MfmaCfg<D>::THREADS / 256)) lfa_attn_pf(LfaArgs A) {
+    using C = MfmaCfg<D>;
+    static_assert(D >= 128, "lfa_attn_pf: D in {128, 256}");
+    constexpr int H = C::H, ROWS = C::ROWS, XP = C::XP, RP = C::RP, THREADS = C::THREADS;
+    constexpr int HP = C::NT2 * 32;                               // lse weight pitch (column tiles, zero padded)
+    HIP_DYNAMIC_SHARED(float, smem)
+    float* X = smem;                                              // [ROWS][XP]
+    float* R1 = X + ROWS * XP;                                    // [ROWS][RP]   (stage 2)
+    float* REL = R1 + (STAGE == 2 ? ROWS * RP : 0);               // [ROWS][12]
+    float* W1 = REL + ROWS * 12;                                  // [12][HP]
+    float* W2 = W1 + 12 * HP;                                     // [H][HP]      (stage 2)
+    uint32_t* NROWG = reinterpret_cast<uint32_t*>(W2 + (STAGE == 2 ? H * HP : 0));   // [ROWS] global neighbour row (SPLIT)
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int hi = lane >> 5, col = lane & 31;
+
+    const int ct = wave % C::NT, rg = wave / C::NT;
+    constexpr int KS = SPLIT ? H : D, K0 = SPLIT ? H : 0;         // score MFMAs run over input channels [K0, K0 + KS)
+    float bs[KS / 2];
+#pragma unroll
+    for (int s = 0; s < KS / 2; ++s) bs[s] = A.score_wt[(K0 + hi * (KS / 2) + s) * D + ct * 32 + col];
+    const float sbias = A.score_b[ct * 32 + col];
+    const int ct2 = wave % C::NT2, rg2 = wave / C::NT2;
+    const int col2 = ct2 * 32 + col;
+    for (int e = tid; e < 12 * HP; e += THREADS) {
+        const int k = e / HP, c = e - k * HP;
+        W1[e] = (k < 10 && c < H) ? A.lse1_wt[k * H + c] : 0.f;
+    }
+    float l2bias = 0.f;
+    if constexpr (STAGE == 2) {
+        for (int e = tid; e < H * HP; e += THREADS) {
+            const int k = e / HP, c = e - k * HP;
+            W2[e] = c < H ? A.lse2_wt[k * H + c] : 0.f;
+        }
+        l2bias = col2 < H ? A.lse2_b[col2] : 0.f;
+    }
+    const float b1 = col2 < H ? A.lse1_b[col2] : 0.f;
+
+    // (the prefetch before the walk: the other way round the D = 256, stage 2, no-SPLIT instances, which sit on the 256-VGPR
+    //  limit, spill two more registers -- profiles/randla_attn_dedup.md)
+    TilePrefetch<C, D, ORD, 12, false, SPLIT> pre;               // REL [ROWS][12], K slots 10, 11 zero: lse1's bias is b1
+    TileWalk<int64_t> walk(A.xcd_chunk, (A.m_total + C::TP - 1) / C::TP, 1, 0);
+
+    int64_t cur = walk.next();
+    if (cur >= 0) { pre.request_idx(A, tid, (uint32_t)cur); pre.request_data(A, tid, (uint32_t)cur); }
+    block_sync_lds();                                            // W1 / W2 staged
+    while (cur >= 0) {
+        const int64_t nxt = walk.next();
+        const int64_t m_base = cur * C::TP;
+        pre.to_lds(tid, X, REL, NROWG);
+        if (nxt >= 0) pre.request_idx(A, tid, (uint32_t)nxt);
         block_sync_lds();
-        // ---- r1 = lrelu(lse1(rel)) on MFMA (K = 12) -> X[:, H:] (stage 1 / in place) or R1 -----------------
+        // ---- r1 = lrelu(lse1(rel)) on MFMA (K = 12) -> X[:, H:] (stage 1) or R1 -----------------------------
         for (int rt = rg2; rt < C::RT; rt += C::RG2) {
             f32x16 acc;
 #pragma unroll
@@ -747,20 +917,18 @@ __global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (D <= 64 ? 3 : (MfmaCfg
                 for (int r = 0; r < 16; ++r) {
                     const int row = rt * 32 + mfma_row(r, hi);
                     const float v = lrelu_max(acc[r], 0.2f);
-                    if (STAGE == 1 || C::INPLACE) X[row * XP + H + col2] = v; else R1[row * RP + col2] = v;
+                    if (STAGE == 1) X[row * XP + H + col2] = v; else R1[row * RP + col2] = v;
                 }
             }
         }
         if constexpr (STAGE == 2) {
-            // in place the row tile's r1 was written by this very wave; otherwise other waves' columns are needed
-            if constexpr (C::INPLACE) wave_lds_sync(); else block_sync_lds();
+            block_sync_lds();                                     // a row tile's r1 columns come from several waves
             // ---- r2 = lrelu(lse2(r1)) on MFMA -> X[:, H:] ------------------------------------------------
             for (int rt = rg2; rt < C::RT; rt += C::RG2) {
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = l2bias;
-                const float* ar = C::INPLACE ? X + (rt * 32 + col) * XP + H + hi * (H / 2)
-                                             : R1 + (rt * 32 + col) * RP + hi * (H / 2);
+                const float* ar = R1 + (rt * 32 + col) * RP + hi * (H / 2);
                 const float* wb = W2 + hi * (H / 2) * HP + col2;
 #pragma unroll
                 for (int s4 = 0; s4 < H / 8; ++s4) {
@@ -777,7 +945,7 @@ __global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (D <= 64 ? 3 : (MfmaCfg
                 }
             }
         }
-        if (nxt >= 0) request_data((uint32_t)nxt);
+        if (nxt >= 0) pre.request_data(A, tid, (uint32_t)nxt);
         block_sync_lds();
         // ---- scores on MFMA, softmax over the 16 neighbours, weighted sum ------------------------------
         for (int rt = rg; rt < C::RT; rt += C::RG) {
@@ -785,19 +953,8 @@ __global__ void __launch_bounds__((MfmaCfg<D>::THREADS), (D <= 64 ? 3 : (MfmaCfg
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = sbias;
             float gs[SPLIT ? 16 : 1];
-            if constexpr (SPLIT) {
-                // the neighbours' per-point score halves, requested before the MFMA chain and added after it
-                const char* gbase = reinterpret_cast<const char*>(A.gscore + ct * 32);    // wave-uniform base
-                const uint32_t col4 = 4u * col;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const uint4 nr = *reinterpret_cast<const uint4*>(NROWG + rt * 32 + 8 * q4 + 4 * hi);   // rows mfma_row(4 q4 .. 4 q4 + 3)
-                    gs[4 * q4 + 0] = *reinterpret_cast<const float*>(gbase + (nr.x + col4));
-                    gs[4 * q4 + 1] = *reinterpret_cast<const float*>(gbase + (nr.y + col4));
-                    gs[4 * q4 + 2] = *reinterpret_cast<const float*>(gbase + (nr.z + col4));
-                    gs[4 * q4 + 3] = *reinterpret_cast<const float*>(gbase + (nr.w + col4));
-                }
-            }
+            // the neighbours' per-point score halves, requested before the MFMA chain and added after it
+            if constexpr (SPLIT) gscore_gather_tile(A.gscore + ct * 32, NROWG + rt * 32, hi, col, gs);
             acc = mfma_rows<KS, XP>(X + (rt * 32 + col) * XP + K0 + hi * (KS / 2), bs, acc);
             if constexpr (SPLIT) {
 #pragma unroll
@@ -824,14 +981,14 @@ template <int D, int STAGE>
 static size_t pf_smem_bytes() {
     using C = MfmaCfg<D>;
     constexpr int HP = C::NT2 * 32;
-    return ((size_t)C::ROWS * C::XP + ((STAGE == 2 && !C::INPLACE) ? (size_t)C::ROWS * C::RP : 0) + (size_t)C::ROWS * 12 +
+    return ((size_t)C::ROWS * C::XP + (STAGE == 2 ? (size_t)C::ROWS * C::RP : 0) + (size_t)C::ROWS * 12 +
             12 * HP + (STAGE == 2 ? (size_t)C::H * HP : 0) + (size_t)C::ROWS) * 4;
 }
 
 
 // ------------------------------------------------------------------------------------------------
 // lfa_attn_wave (D <= 64) — the attention stage with NO workgroup barrier in the tile loop.
-// In lfa_attn_mfma / lfa_attn_pf a workgroup's waves split the column tiles of one 128-row tile, so
+// In a workgroup-tile kernel (lfa_attn_pf) a workgroup's waves split the column tiles of one row tile, so
 // they meet at 3-4 barriers per tile; with one wave of each resident workgroup per SIMD, any wave that
 // queues behind another workgroup's MFMAs stalls its three siblings on the other SIMDs (measured:
 // removing the score MFMAs, 74 % of the MFMA work, removes more time than they take at peak, i.e. the
@@ -847,8 +1004,6 @@ struct WaveAttnCfg {
     static constexpr int H = D / 2;
     static constexpr int NT = D / 32;
     static constexpr int XP = D + 4;
-    static constexpr int Q = H / 4;                  // float4 pieces per gathered row
-    static constexpr int G = 32 * Q / 64;            // pieces per lane
     static constexpr int W = D == 64 ? 12 : 16;      // waves per workgroup
     static constexpr int PATCH = 32 * XP + 32 * 12 + 32;  // floats per wave: X, relative positions, gscore row offsets
     static constexpr int WFLOATS = D * D + H * 32 + 12 * 32;
@@ -860,8 +1015,8 @@ struct WaveAttnCfg {
 template <int D, int STAGE, bool SPLIT, bool ORD>
 __global__ void __launch_bounds__((WaveAttnCfg<D>::W * 64)) lfa_attn_wave(LfaArgs A) {
     using C = WaveAttnCfg<D>;
-    constexpr int H = C::H, XP = C::XP, Q = C::Q, G = C::G, NT = C::NT;
-    static_assert(H <= 32 && (32 * Q) % 64 == 0, "lfa_attn_wave: D in {32, 64}");
+    constexpr int H = C::H, XP = C::XP, NT = C::NT;
+    static_assert(H <= 32, "lfa_attn_wave: D in {32, 64}");
     HIP_DYNAMIC_SHARED(float, smem)
     float* WS = smem;                                 // [D][D]   score weights (transposed Linear: [in][out])
     float* W2 = WS + D * D;                           // [H][32]  lse2 (zero padded columns)
@@ -893,129 +1048,21 @@ __global__ void __launch_bounds__((WaveAttnCfg<D>::W * 64)) lfa_attn_wave(LfaArg
     // scalar explicitly): the f32 MFMAs and the VALU share the SIMD's issue cycles on gfx950 (tools/micro), so
     // every vector instruction outside the MFMAs is paid in full.  Point indices fit 32 bits (launcher checks).
     const int swave = __builtin_amdgcn_readfirstlane(wave);
-    const uint32_t tiles = (uint32_t)((A.m_total + 1) / 2);       // 2 points per wave tile
-    const uint32_t n_pts = (uint32_t)A.n, m_tot = (uint32_t)A.m_total;
-    const bool xw = A.xcd_chunk > 0;
-    const uint32_t w_step = (xw ? (gridDim.x >> 3) : gridDim.x) * C::W;
-    uint32_t wi = (xw ? (blockIdx.x >> 3) : blockIdx.x) * C::W + swave;
-    auto next_tile = [&]() -> int64_t {
-        for (;;) {
-            int64_t t = wi;
-            if (xw) t = xcd_tile((int64_t)wi, (int)(blockIdx.x & 7), A.xcd_chunk, (int64_t)tiles);
-            wi += w_step;
-            if (t < 0) return -1;
-            if (t < (int64_t)tiles) return t;
-            if (!xw) return -1;
-        }
-    };
+    const uint32_t m_tot = (uint32_t)A.m_total;
+    TileWalk<uint32_t> walk(A.xcd_chunk, (uint32_t)((A.m_total + 1) / 2), C::W, (uint32_t)swave);   // 2 points per wave tile
+    WavePrefetch<D, ORD, SPLIT> pre;
 
-    int gi[G], nb_mine = -1;
-    float4 gq[G];
-    float qx = 0.f, qy = 0.f, qz = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-    bool mine_valid = false;
-    uint32_t goff_mine = 0;
-    uint32_t mo0 = 0, mo1 = 0;           // ORD: the tile's two point rows (order[2 t], order[2 t + 1]; wave-uniform values)
-    auto request_idx = [&](uint32_t tile) {
-        const uint32_t lim = (m_tot - tile * 2) >= 2 ? 32u : 16u; // rows of the tile that exist
-        if constexpr (ORD) {
-            mo0 = (uint32_t)A.order[tile * 2];
-            mo1 = lim == 32u ? (uint32_t)A.order[tile * 2 + 1] : mo0;
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const uint32_t row = (uint32_t)(lane + 64 * i) / Q;
-                gi[i] = row < lim ? __builtin_nontemporal_load(A.nidx + (int64_t)(row < RK ? mo0 : mo1) * RK + (row & (RK - 1))) : -1;
-            }
-            nb_mine = (uint32_t)lane < lim
-                          ? __builtin_nontemporal_load(A.nidx + (int64_t)(lane < RK ? mo0 : mo1) * RK + (lane & (RK - 1))) : -1;
-        } else {
-            const int32_t* nb = A.nidx + (int64_t)tile * 2 * RK;  // 32 contiguous (point, neighbour) rows
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const uint32_t row = (uint32_t)(lane + 64 * i) / Q;
-                gi[i] = row < lim ? __builtin_nontemporal_load(nb + row) : -1;
-            }
-            nb_mine = (uint32_t)lane < lim ? __builtin_nontemporal_load(nb + lane) : -1;
-        }
-    };
-    auto request_data = [&](uint32_t tile) {
-        // the tile's two points: cloud b0 / local index l0, and its successor (possibly the next cloud's first point);
-        // ORD: two arbitrary rows, each located by its own scalar division
-        uint32_t b0, l0, b1, l1;
-        if constexpr (ORD) {
-            const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo0);
-            const uint32_t m1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo1);
-            b0 = m0 / n_pts; l0 = m0 - b0 * n_pts;
-            b1 = m1 / n_pts; l1 = m1 - b1 * n_pts;
-        } else {
-            const uint32_t m0 = tile * 2;
-            b0 = m0 / n_pts; l0 = m0 - b0 * n_pts;
-            const bool wrap = l0 + 1 == n_pts;
-            b1 = wrap ? b0 + 1 : b0; l1 = wrap ? 0u : l0 + 1;
-        }
-        const float* f0 = A.gfeat + (int64_t)b0 * n_pts * H;      // scalar bases, 32-bit lane offsets
-        const float* f1 = A.gfeat + (int64_t)b1 * n_pts * H;
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int e = lane + 64 * i;
-            const int row = e / Q, q = e - row * Q;
-            gq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gi[i] >= 0) gq[i] = *reinterpret_cast<const float4*>((row < RK ? f0 : f1) + (uint32_t)gi[i] * H + 4 * q);
-        }
-        mine_valid = lane < 32 && nb_mine >= 0;
-        if (mine_valid) {
-            const bool p1 = lane >= RK;
-            goff_mine = ((p1 ? b1 : b0) * n_pts + (uint32_t)nb_mine) * (uint32_t)(D * 4);
-            const float* xb = A.xyz + 3 * ((int64_t)(p1 ? b1 : b0) * A.n0);
-            const float* qp = xb + 3 * (p1 ? l1 : l0);
-            const float* sp = xb + 3 * (uint32_t)nb_mine;
-            qx = qp[0]; qy = qp[1]; qz = qp[2]; sx = sp[0]; sy = sp[1]; sz = sp[2];
-        }
-    };
-
-    int64_t cur = next_tile();
-    if (cur >= 0) { request_idx((uint32_t)cur); request_data((uint32_t)cur); }
+    int64_t cur = walk.next();
+    if (cur >= 0) { pre.request_idx(A, lane, (uint32_t)cur); pre.request_data(A, lane, (uint32_t)cur); }
     while (cur >= 0) {
-        const int64_t nxt = next_tile();
-        const uint32_t mo0_cur = mo0, mo1_cur = mo1;             // (request_idx(nxt) overwrites them)
-        // ---- registers -> the wave's patch ---------------------------------------------------------------
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int e = lane + 64 * i;
-            const int row = e / Q, q = e - row * Q;
-            *reinterpret_cast<float4*>(X + row * XP + 4 * q) = gq[i];
-        }
-        if (lane < 32) {
-            float* r = REL + lane * 12;
-            if (mine_valid) {
-                const float dx = qx - sx, dy = qy - sy, dz = qz - sz;
-                r[0] = sqrtf(dx * dx + dy * dy + dz * dz);
-                r[1] = dx; r[2] = dy; r[3] = dz; r[4] = qx; r[5] = qy; r[6] = qz; r[7] = sx; r[8] = sy; r[9] = sz;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 10; ++j) r[j] = 0.f;
-            }
-            r[10] = 1.f; r[11] = 0.f;                             // bias slot, K padding
-            if constexpr (SPLIT) GOFF[lane] = mine_valid ? goff_mine : 0u;    // (rows past the data read row 0: never stored)
-        }
-        if (nxt >= 0) request_idx((uint32_t)nxt);
+        const int64_t nxt = walk.next();
+        const uint32_t mo0_cur = pre.mo0, mo1_cur = pre.mo1;     // (request_idx(nxt) overwrites them)
+        pre.to_patch(lane, X, REL, GOFF);
+        if (nxt >= 0) pre.request_idx(A, lane, (uint32_t)nxt);
         wave_lds_sync();
         f32x16 sc[NT];
-        if constexpr (SPLIT) {
-            // the neighbours' per-point score halves become the accumulators' initial value
-            const char* gbase = reinterpret_cast<const char*>(A.gscore);
-            const uint32_t col4 = 4u * col;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const uint4 go = *reinterpret_cast<const uint4*>(GOFF + 8 * q4 + 4 * hi);     // rows mfma_row(4 q4 .. 4 q4 + 3)
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    sc[t][4 * q4 + 0] = *reinterpret_cast<const float*>(gbase + (go.x + col4 + 128u * t));
-                    sc[t][4 * q4 + 1] = *reinterpret_cast<const float*>(gbase + (go.y + col4 + 128u * t));
-                    sc[t][4 * q4 + 2] = *reinterpret_cast<const float*>(gbase + (go.z + col4 + 128u * t));
-                    sc[t][4 * q4 + 3] = *reinterpret_cast<const float*>(gbase + (go.w + col4 + 128u * t));
-                }
-            }
-        }
+        // SPLIT: the neighbours' per-point score halves become the accumulators' initial value
+        if constexpr (SPLIT) gscore_gather_wave(A.gscore, GOFF, hi, col, sc);
         // ---- r1 = lrelu(lse1(rel)) (K = 12) -> X[:, H:] ---------------------------------------------------
         {
             f32x16 acc;
@@ -1068,7 +1115,7 @@ __global__ void __launch_bounds__((WaveAttnCfg<D>::W * 64)) lfa_attn_wave(LfaArg
             }
             wave_lds_sync();
         }
-        if (nxt >= 0) request_data((uint32_t)nxt);
+        if (nxt >= 0) pre.request_data(A, lane, (uint32_t)nxt);
         // ---- scores for all column tiles (A read once), softmax over the 16 neighbours, weighted sum --------
         if constexpr (!SPLIT) {
 #pragma unroll
@@ -1140,7 +1187,7 @@ static int launch_attn_wave(LfaArgs a, hipStream_t st) {
 //     its 8 waves) and the barriers are amortised over twice the rows.
 // LDS: X [ROWS][D + 4] f32 (gathered features | r) for the weighted sum, ONE set of planes [3][ROWS][H + 8] bf16 that
 // holds r1 and then r2 (a barrier between lse2's last read and its first write), REL [ROWS][13], NROWG [ROWS]:
-// 122 KB (D = 256) / 130 KB (D = 128), one workgroup per CU.  Prefetch of the next tile's gathers exactly as lfa_attn_pf.
+// 122 KB (D = 256) / 130 KB (D = 128), one workgroup per CU.  Prefetch of the next tile's gathers: TilePrefetch, as lfa_attn_pf.
 // lse1 (K = 10 + bias slot) stays on the f32 MFMA (16 x 16 x 4: three per 16 x 16 block, the same count the bf16x3 form needs).
 // ------------------------------------------------------------------------------------------------
 template <int D, int STAGE>
@@ -1202,10 +1249,7 @@ __device__ __forceinline__ void b3_split8(const float (&v)[8], ml3d_u32x4& h, ml
 template <int D, int STAGE, bool ORD>
 __global__ void __launch_bounds__((B3Cfg<D, STAGE>::THREADS / ML3D_B3_LB_DIV)) lfa_attn_b3(LfaArgs A) {
     using C = B3Cfg<D, STAGE>;
-    constexpr int H = C::H, ROWS = C::ROWS, XP = C::XP, PP = C::PP, RELP = C::RELP, THREADS = C::THREADS;
-    constexpr int Q = H / 4;                                      // float4 pieces per gathered row
-    constexpr int G = ROWS * Q / THREADS;                         // pieces per thread
-    static_assert(ROWS * Q % THREADS == 0 && ROWS <= THREADS, "tile shape");
+    constexpr int H = C::H, ROWS = C::ROWS, XP = C::XP, PP = C::PP, RELP = C::RELP;
     HIP_DYNAMIC_SHARED(float, smem)
     float* X = smem;                                              // [ROWS][XP]
     uint16_t* PL = reinterpret_cast<uint16_t*>(X + ROWS * XP);    // [3][ROWS][PP] bf16: r1, then r2
@@ -1247,97 +1291,8 @@ __global__ void __launch_bounds__((B3Cfg<D, STAGE>::THREADS / ML3D_B3_LB_DIV)) l
         w1[s] = k < 10 ? A.lse1_wt[k * H + ch0 + l16] : (k == 10 ? A.lse1_b[ch0 + l16] : 0.f);
     }
 
-    const int64_t tiles = (A.m_total + C::TP - 1) / C::TP;
-    const bool xw = A.xcd_chunk > 0;
-    const int64_t w_step = xw ? (int64_t)(gridDim.x >> 3) : (int64_t)gridDim.x;
-    int64_t wi = xw ? (int64_t)(blockIdx.x >> 3) : (int64_t)blockIdx.x;
-    auto next_tile = [&]() -> int64_t {
-        for (;;) {
-            int64_t t = wi;
-            if (xw) t = xcd_tile(wi, (int)(blockIdx.x & 7), A.xcd_chunk, tiles);
-            wi += w_step;
-            if (t < 0) return -1;
-            if (t < tiles) return t;
-            if (!xw) return -1;
-        }
-    };
-
-    // ---- this thread's slots of a tile's inputs (as lfa_attn_pf) ---------------------------------------------------
-    int gi[G], nb_mine = 0;
-    float4 gq[G];
-    float qx = 0.f, qy = 0.f, qz = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-    bool mine_valid = false;
-    uint32_t grow_mine = 0;
-    const uint32_t n_pts = (uint32_t)A.n, m_tot = (uint32_t)A.m_total;
-    uint32_t gmp[ORD ? G : 1], mp_mine = 0, m_first = 0;
-    auto request_idx = [&](uint32_t tile) {
-        const uint32_t have = m_tot - tile * C::TP;
-        const uint32_t lim = (have < (uint32_t)C::TP ? have : (uint32_t)C::TP) * RK;
-        if constexpr (ORD) {
-            const int32_t* ord = A.order + tile * C::TP;
-            m_first = (uint32_t)ord[0];
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const uint32_t row = (uint32_t)(tid + i * THREADS) / Q;
-                gi[i] = -1;
-                if (row < lim) {
-                    gmp[i] = (uint32_t)ord[row / RK];
-                    gi[i] = A.nidx[(int64_t)gmp[i] * RK + (row & (RK - 1))];
-                }
-            }
-            if (tid < ROWS) {
-                nb_mine = -1;
-                if ((uint32_t)tid < lim) {
-                    mp_mine = (uint32_t)ord[tid / RK];
-                    nb_mine = A.nidx[(int64_t)mp_mine * RK + (tid & (RK - 1))];
-                }
-            }
-        } else {
-            const int32_t* nb = A.nidx + (int64_t)tile * (C::TP * RK);
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const uint32_t row = (uint32_t)(tid + i * THREADS) / Q;
-                gi[i] = row < lim ? nb[row] : -1;
-            }
-            if (tid < ROWS) nb_mine = (uint32_t)tid < lim ? nb[tid] : -1;
-        }
-    };
-    auto request_data = [&](uint32_t tile) {
-        const uint32_t m0 = ORD ? (uint32_t)__builtin_amdgcn_readfirstlane((int)m_first) : tile * C::TP;
-        const uint32_t b0 = m0 / n_pts, l0 = m0 - b0 * n_pts;
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int e = tid + i * THREADS;
-            const int row = e / Q, q = e - row * Q;
-            gq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gi[i] >= 0) {
-                uint32_t b;
-                if constexpr (ORD) b = b0 + (gmp[i] >= (b0 + 1) * n_pts ? 1u : 0u);
-                else b = b0 + ((l0 + (uint32_t)(row / RK) >= n_pts) ? 1u : 0u);
-                gq[i] = *reinterpret_cast<const float4*>(A.gfeat + ((int64_t)b * n_pts + (uint32_t)gi[i]) * H + 4 * q);
-            }
-        }
-        if (tid < ROWS) {
-            mine_valid = nb_mine >= 0;
-            if (mine_valid) {
-                uint32_t b, l;
-                if constexpr (ORD) {
-                    b = b0 + (mp_mine >= (b0 + 1) * n_pts ? 1u : 0u);
-                    l = mp_mine - b * n_pts;
-                } else {
-                    const uint32_t lp = l0 + (uint32_t)(tid / RK);
-                    const bool wrap = lp >= n_pts;
-                    b = b0 + (wrap ? 1u : 0u);
-                    l = wrap ? lp - n_pts : lp;
-                }
-                grow_mine = b * n_pts + (uint32_t)nb_mine;
-                const float* xb = A.xyz + 3 * ((int64_t)b * A.n0);
-                const float* qp = xb + 3 * l;
-                const float* sp = xb + 3 * (uint32_t)nb_mine;
-                qx = qp[0]; qy = qp[1]; qz = qp[2]; sx = sp[0]; sy = sp[1]; sz = sp[2];
-            }
-        }
-    };
+    TilePrefetch<C, D, ORD, RELP, true, true> pre;               // REL [ROWS][RELP] with the bias slot, NROWG always (gscore)
+    TileWalk<int64_t> walk(A.xcd_chunk, (A.m_total + C::TP - 1) / C::TP, 1, 0);
     // one 16 x 16 block of r (C^T layout: this lane holds channels ch0 + 4 kq .. + 3 of row `row`) -> the planes [+ X]
     auto store_r = [&](int row, const ml3d_f32x4& acc, bool to_x) {
         const float v0 = lrelu_max(acc[0], 0.2f), v1 = lrelu_max(acc[1], 0.2f), v2 = lrelu_max(acc[2], 0.2f),
@@ -1351,32 +1306,13 @@ __global__ void __launch_bounds__((B3Cfg<D, STAGE>::THREADS / ML3D_B3_LB_DIV)) l
         if (to_x) *reinterpret_cast<float4*>(X + row * XP + H + ch0 + 4 * kq) = make_float4(v0, v1, v2, v3);
     };
 
-    int64_t cur = next_tile();
-    if (cur >= 0) { request_idx((uint32_t)cur); request_data((uint32_t)cur); }
+    int64_t cur = walk.next();
+    if (cur >= 0) { pre.request_idx(A, tid, (uint32_t)cur); pre.request_data(A, tid, (uint32_t)cur); }
     while (cur >= 0) {
-        const int64_t nxt = next_tile();
+        const int64_t nxt = walk.next();
         const int64_t m_base = cur * C::TP;
-        // ---- registers -> LDS -----------------------------------------------------------------------
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int e = tid + i * THREADS;
-            const int row = e / Q, q = e - row * Q;
-            *reinterpret_cast<float4*>(X + row * XP + 4 * q) = gq[i];
-        }
-        if (tid < ROWS) {
-            float* r = REL + tid * RELP;
-            if (mine_valid) {
-                const float dx = qx - sx, dy = qy - sy, dz = qz - sz;
-                r[0] = sqrtf(dx * dx + dy * dy + dz * dz);
-                r[1] = dx; r[2] = dy; r[3] = dz; r[4] = qx; r[5] = qy; r[6] = qz; r[7] = sx; r[8] = sy; r[9] = sz;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 10; ++j) r[j] = 0.f;
-            }
-            r[10] = 1.f; r[11] = 0.f;                              // bias slot, K padding
-            NROWG[tid] = mine_valid ? grow_mine * (uint32_t)(D * 4) : 0u;    // (rows past the data read row 0: never stored)
-        }
-        if (nxt >= 0) request_idx((uint32_t)nxt);
+        pre.to_lds(tid, X, REL, NROWG);
+        if (nxt >= 0) pre.request_idx(A, tid, (uint32_t)nxt);
         block_sync_lds();
         // ---- r1 = lrelu(lse1(rel)), transposed on the f32 MFMA (K = 12) -> planes (stage 1: + X[:, H:]) -------------
 #pragma unroll 1
@@ -1392,22 +1328,8 @@ __global__ void __launch_bounds__((B3Cfg<D, STAGE>::THREADS / ML3D_B3_LB_DIV)) l
         // the neighbours' per-point score halves (gscore = f . W_top^T + bias, one row per POINT) become the score accumulators'
         // initial values: requested here, they land under the lse2 MFMAs / the barriers
         f32x16 sacc[C::SRT];
-        {
-            const char* gbase = reinterpret_cast<const char*>(A.gscore + ct * 32);    // wave-uniform base
-            const uint32_t col4 = 4u * col;
 #pragma unroll
-            for (int j = 0; j < C::SRT; ++j) {
-                const int rt = rg + C::RG * j;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const uint4 nr = *reinterpret_cast<const uint4*>(NROWG + rt * 32 + 8 * q4 + 4 * hi);   // rows mfma_row(4 q4 .. 4 q4 + 3)
-                    sacc[j][4 * q4 + 0] = *reinterpret_cast<const float*>(gbase + (nr.x + col4));
-                    sacc[j][4 * q4 + 1] = *reinterpret_cast<const float*>(gbase + (nr.y + col4));
-                    sacc[j][4 * q4 + 2] = *reinterpret_cast<const float*>(gbase + (nr.z + col4));
-                    sacc[j][4 * q4 + 3] = *reinterpret_cast<const float*>(gbase + (nr.w + col4));
-                }
-            }
-        }
+        for (int j = 0; j < C::SRT; ++j) gscore_gather_tile(A.gscore + ct * 32, NROWG + (rg + C::RG * j) * 32, hi, col, sacc[j]);
         if constexpr (STAGE == 2) {
             block_sync_lds();
             // ---- r2 = lrelu(lse2(r1)), transposed on the bf16 pipe; every read of r1 precedes the first write of r2 ------
@@ -1441,7 +1363,7 @@ __global__ void __launch_bounds__((B3Cfg<D, STAGE>::THREADS / ML3D_B3_LB_DIV)) l
 #pragma unroll
             for (int j = 0; j < C::LRT; ++j) store_r((rg2 + C::RG2 * j) * 16 + l16, acc2[j], true);
         }
-        if (nxt >= 0) request_data((uint32_t)nxt);
+        if (nxt >= 0) pre.request_data(A, tid, (uint32_t)nxt);
         block_sync_lds();
         // ---- scores on the bf16 pipe (K = H: the position half; the feature half arrives as gscore), softmax, weighted sum ---
 #pragma unroll
@@ -1517,7 +1439,6 @@ struct WaveB3Cfg {
     static constexpr int H = D / 2;                 // 32
     static constexpr int NT = D / 32;               // score column tiles
     static constexpr int XP = D + 4;
-    static constexpr int Q = H / 4, G = 32 * Q / 64;
     static constexpr int W = 12;                    // waves per workgroup
     static constexpr int PATCH = 32 * XP + 32 * 12 + 32;     // floats per wave: X, relative positions, gscore row offsets
     static constexpr int WP = H + 8;                // bf16 pitch of a weight row (K = H + 16 bytes: conflict-free b128 fragments)
@@ -1529,7 +1450,7 @@ struct WaveB3Cfg {
 template <int D, int STAGE, bool ORD>
 __global__ void __launch_bounds__((WaveB3Cfg<D>::W * 64)) lfa_attn_wave_b3(LfaArgs A) {
     using C = WaveB3Cfg<D>;
-    constexpr int H = C::H, XP = C::XP, Q = C::Q, G = C::G, NT = C::NT, WP = C::WP;
+    constexpr int H = C::H, XP = C::XP, NT = C::NT, WP = C::WP;
     HIP_DYNAMIC_SHARED(float, smem)
     uint16_t* WS = reinterpret_cast<uint16_t*>(smem);            // [3][D][WP]   score_WT[H + k][col] as planes[col][k]
     uint16_t* W2 = WS + 3 * C::WSP;                               // [3][H][WP]   lse2_WT[k][ch] as planes[ch][k]
@@ -1574,82 +1495,9 @@ __global__ void __launch_bounds__((WaveB3Cfg<D>::W * 64)) lfa_attn_wave_b3(LfaAr
     __syncthreads();                                  // the only workgroup barrier
 
     const int swave = __builtin_amdgcn_readfirstlane(wave);
-    const uint32_t tiles = (uint32_t)((A.m_total + 1) / 2);       // 2 points per wave tile
-    const uint32_t n_pts = (uint32_t)A.n, m_tot = (uint32_t)A.m_total;
-    const bool xw = A.xcd_chunk > 0;
-    const uint32_t w_step = (xw ? (gridDim.x >> 3) : gridDim.x) * C::W;
-    uint32_t wi = (xw ? (blockIdx.x >> 3) : blockIdx.x) * C::W + swave;
-    auto next_tile = [&]() -> int64_t {
-        for (;;) {
-            int64_t t = wi;
-            if (xw) t = xcd_tile((int64_t)wi, (int)(blockIdx.x & 7), A.xcd_chunk, (int64_t)tiles);
-            wi += w_step;
-            if (t < 0) return -1;
-            if (t < (int64_t)tiles) return t;
-            if (!xw) return -1;
-        }
-    };
-
-    int gi[G], nb_mine = -1;
-    float4 gq[G];
-    float qx = 0.f, qy = 0.f, qz = 0.f, sx = 0.f, sy = 0.f, sz = 0.f;
-    bool mine_valid = false;
-    uint32_t goff_mine = 0;
-    uint32_t mo0 = 0, mo1 = 0;
-    auto request_idx = [&](uint32_t tile) {
-        const uint32_t lim = (m_tot - tile * 2) >= 2 ? 32u : 16u;
-        if constexpr (ORD) {
-            mo0 = (uint32_t)A.order[tile * 2];
-            mo1 = lim == 32u ? (uint32_t)A.order[tile * 2 + 1] : mo0;
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const uint32_t row = (uint32_t)(lane + 64 * i) / Q;
-                gi[i] = row < lim ? __builtin_nontemporal_load(A.nidx + (int64_t)(row < RK ? mo0 : mo1) * RK + (row & (RK - 1))) : -1;
-            }
-            nb_mine = (uint32_t)lane < lim
-                          ? __builtin_nontemporal_load(A.nidx + (int64_t)(lane < RK ? mo0 : mo1) * RK + (lane & (RK - 1))) : -1;
-        } else {
-            const int32_t* nb = A.nidx + (int64_t)tile * 2 * RK;
-#pragma unroll
-            for (int i = 0; i < G; ++i) {
-                const uint32_t row = (uint32_t)(lane + 64 * i) / Q;
-                gi[i] = row < lim ? __builtin_nontemporal_load(nb + row) : -1;
-            }
-            nb_mine = (uint32_t)lane < lim ? __builtin_nontemporal_load(nb + lane) : -1;
-        }
-    };
-    auto request_data = [&](uint32_t tile) {
-        uint32_t b0, l0, b1, l1;
-        if constexpr (ORD) {
-            const uint32_t m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo0);
-            const uint32_t m1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mo1);
-            b0 = m0 / n_pts; l0 = m0 - b0 * n_pts;
-            b1 = m1 / n_pts; l1 = m1 - b1 * n_pts;
-        } else {
-            const uint32_t m0 = tile * 2;
-            b0 = m0 / n_pts; l0 = m0 - b0 * n_pts;
-            const bool wrap = l0 + 1 == n_pts;
-            b1 = wrap ? b0 + 1 : b0; l1 = wrap ? 0u : l0 + 1;
-        }
-        const float* f0 = A.gfeat + (int64_t)b0 * n_pts * H;
-        const float* f1 = A.gfeat + (int64_t)b1 * n_pts * H;
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int e = lane + 64 * i;
-            const int row = e / Q, q = e - row * Q;
-            gq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gi[i] >= 0) gq[i] = *reinterpret_cast<const float4*>((row < RK ? f0 : f1) + (uint32_t)gi[i] * H + 4 * q);
-        }
-        mine_valid = lane < 32 && nb_mine >= 0;
-        if (mine_valid) {
-            const bool p1 = lane >= RK;
-            goff_mine = ((p1 ? b1 : b0) * n_pts + (uint32_t)nb_mine) * (uint32_t)(D * 4);
-            const float* xb = A.xyz + 3 * ((int64_t)(p1 ? b1 : b0) * A.n0);
-            const float* qp = xb + 3 * (p1 ? l1 : l0);
-            const float* sp = xb + 3 * (uint32_t)nb_mine;
-            qx = qp[0]; qy = qp[1]; qz = qp[2]; sx = sp[0]; sy = sp[1]; sz = sp[2];
-        }
-    };
+    const uint32_t m_tot = (uint32_t)A.m_total;
+    TileWalk<uint32_t> walk(A.xcd_chunk, (uint32_t)((A.m_total + 1) / 2), C::W, (uint32_t)swave);   // 2 points per wave tile
+    WavePrefetch<D, ORD, true> pre;
     // lrelu of a transposed 32 x 32 result (this lane: row col, channels 8 g + 4 hi .. + 3, g = 0..3) -> the float rows of X[:, H:]
     // and the three-way split as operand fragments of the next product: frag[p][ks] = K 16 ks + 8 hi .. + 7 of row col
     auto finish_r = [&](const f32x16& acc, const float* bias /* LDS [H] or null */, bool to_x, ml3d_u32x4 (&frag)[3][2]) {
@@ -1676,50 +1524,17 @@ __global__ void __launch_bounds__((WaveB3Cfg<D>::W * 64)) lfa_attn_wave_b3(LfaAr
             }
     };
 
-    int64_t cur = next_tile();
-    if (cur >= 0) { request_idx((uint32_t)cur); request_data((uint32_t)cur); }
+    int64_t cur = walk.next();
+    if (cur >= 0) { pre.request_idx(A, lane, (uint32_t)cur); pre.request_data(A, lane, (uint32_t)cur); }
     while (cur >= 0) {
-        const int64_t nxt = next_tile();
-        const uint32_t mo0_cur = mo0, mo1_cur = mo1;
-        // ---- registers -> the wave's patch ---------------------------------------------------------------
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int e = lane + 64 * i;
-            const int row = e / Q, q = e - row * Q;
-            *reinterpret_cast<float4*>(X + row * XP + 4 * q) = gq[i];
-        }
-        if (lane < 32) {
-            float* r = REL + lane * 12;
-            if (mine_valid) {
-                const float dx = qx - sx, dy = qy - sy, dz = qz - sz;
-                r[0] = sqrtf(dx * dx + dy * dy + dz * dz);
-                r[1] = dx; r[2] = dy; r[3] = dz; r[4] = qx; r[5] = qy; r[6] = qz; r[7] = sx; r[8] = sy; r[9] = sz;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 10; ++j) r[j] = 0.f;
-            }
-            r[10] = 1.f; r[11] = 0.f;                             // bias slot, K padding
-            GOFF[lane] = mine_valid ? goff_mine : 0u;             // (rows past the data read row 0: never stored)
-        }
-        if (nxt >= 0) request_idx((uint32_t)nxt);
+        const int64_t nxt = walk.next();
+        const uint32_t mo0_cur = pre.mo0, mo1_cur = pre.mo1;     // (request_idx(nxt) overwrites them)
+        pre.to_patch(lane, X, REL, GOFF);
+        if (nxt >= 0) pre.request_idx(A, lane, (uint32_t)nxt);
         wave_lds_sync();
         // the neighbours' per-point score halves (gscore, bias included) become the accumulators' initial value
         f32x16 sc[NT];
-        {
-            const char* gbase = reinterpret_cast<const char*>(A.gscore);
-            const uint32_t col4 = 4u * col;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const uint4 go = *reinterpret_cast<const uint4*>(GOFF + 8 * q4 + 4 * hi);     // rows mfma_row(4 q4 .. 4 q4 + 3)
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    sc[t][4 * q4 + 0] = *reinterpret_cast<const float*>(gbase + (go.x + col4 + 128u * t));
-                    sc[t][4 * q4 + 1] = *reinterpret_cast<const float*>(gbase + (go.y + col4 + 128u * t));
-                    sc[t][4 * q4 + 2] = *reinterpret_cast<const float*>(gbase + (go.z + col4 + 128u * t));
-                    sc[t][4 * q4 + 3] = *reinterpret_cast<const float*>(gbase + (go.w + col4 + 128u * t));
-                }
-            }
-        }
+        gscore_gather_wave(A.gscore, GOFF, hi, col, sc);
         ml3d_u32x4 frag[3][2];
         // ---- r1^T = lse1_W^T . rel^T on the f32 MFMA (K = 12); lrelu, float rows -> X[:, H:], split -> fragments -----------
         {
@@ -1753,7 +1568,7 @@ __global__ void __launch_bounds__((WaveB3Cfg<D>::W * 64)) lfa_attn_wave_b3(LfaAr
             }
             finish_r(acc, B2, true, frag);
         }
-        if (nxt >= 0) request_data((uint32_t)nxt);
+        if (nxt >= 0) pre.request_data(A, lane, (uint32_t)nxt);
         // ---- scores (A = the fragments, B = weight planes from LDS), softmax over the 16 neighbours, weighted sum ------------
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -1807,7 +1622,11 @@ constexpr bool ATTN_MFMA_WIDTH = D == 16 || D == 32 || D == 64 || D == 128 || D 
 template <int D>
 static bool attn_mfma_fits(const LfaArgs& a) {
     if constexpr (!ATTN_MFMA_WIDTH<D>) return false;
-    else return a.m_total < ((int64_t)1 << 30) && a.n0 < ((int64_t)1 << 30) && (D <= 64 || a.n >= MfmaCfg<D>::TP);
+    else {
+        if (a.m_total >= ((int64_t)1 << 30) || a.n0 >= ((int64_t)1 << 30)) return false;
+        if constexpr (D <= 64) return true;
+        else return a.n >= MfmaCfg<D>::TP;                       // lfa_attn_pf: a tile inside one or two consecutive clouds
+    }
 }
 
 template <int D, int STAGE>
@@ -1899,21 +1718,8 @@ lfa_attn_mfma16(LfaArgs A, const float* __restrict__ lse1_wt, const float* __res
     }
     // tile bookkeeping is wave-uniform and 32-bit (launcher: m_total, n0 < 2^30, n >= 16): the VALU shares the SIMD's
     // issue cycles with the f32 MFMAs on gfx950, a 64-bit division per lane would cost more than the tile's MFMAs
-    const uint32_t tiles = (uint32_t)((A.m_total + A16_TP - 1) / A16_TP);
     const uint32_t n_pts = (uint32_t)A.n, m_tot = (uint32_t)A.m_total;
-    const bool xw = A.xcd_chunk > 0;
-    const uint32_t w_step = xw ? (gridDim.x >> 3) : gridDim.x;
-    uint32_t wi = xw ? (blockIdx.x >> 3) : blockIdx.x;
-    auto next_tile = [&]() -> int64_t {
-        for (;;) {
-            int64_t t = wi;
-            if (xw) t = xcd_tile((int64_t)wi, (int)(blockIdx.x & 7), A.xcd_chunk, (int64_t)tiles);
-            wi += w_step;
-            if (t < 0) return -1;
-            if (t < (int64_t)tiles) return t;
-            if (!xw) return -1;
-        }
-    };
+    TileWalk<uint32_t> walk(A.xcd_chunk, (uint32_t)((A.m_total + A16_TP - 1) / A16_TP), 1, 0);
     // rows 64w .. 64w+63 of a tile (points 4w .. 4w+3) are built AND consumed by wave w: no workgroup barrier
     float* Xw = X + wave * 64 * A16_XP;
     const uint32_t p = tid >> 4;                                              // thread = (point p, neighbour tid & 15) row
@@ -1962,10 +1768,10 @@ lfa_attn_mfma16(LfaArgs A, const float* __restrict__ lse1_wt, const float* __res
         }
     };
     int parked = 0;                      // EPI: tiles whose pooled rows wait in the wave's LDS patch
-    int64_t cur = next_tile();
+    int64_t cur = walk.next();
     if (cur >= 0) { request_idx((uint32_t)cur); request_data((uint32_t)cur); }
     while (cur >= 0) {
-        const int64_t nxt = next_tile();
+        const int64_t nxt = walk.next();
         const uint32_t m_base = (uint32_t)cur * A16_TP;
         const uint32_t mrow_cur = mrow;                                       // (request_idx(nxt) below overwrites mrow)
         {   // ---- build this thread's X row ---------------------------------------------------------

@@ -102,7 +102,7 @@ def lfa_smem_bytes(dd, stage, d_in):
 
 
 def walk(tiles, grid, tiles_per_wg, chunk):
-    """next_tile of the attention kernels: every worker slot's tiles -> (most tiles one slot takes); every tile exactly once."""
+    """TileWalk::next of the attention kernels: every worker slot's tiles -> (most tiles one slot takes); every tile exactly once."""
     seen = np.zeros(tiles, np.int32)
     most = 0
     if chunk == 0:
