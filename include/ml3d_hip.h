@@ -696,6 +696,54 @@ int ml3d_patch_batch(const float* points, double* possibility, const int64_t* cl
                      float* out_pts, float* out_features, int32_t* out_sel, int32_t* out_row,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the input-sphere loop of KPFCNN for SEVERAL clouds in lock step (multi-cloud sphere loop) -- */
+/* kpconv.py:446-531 around the radius sampler of semseg_spatially_regular.py:62-108: a cloud's     */
+/* spheres depend only on its possibilities and its own random draws, so one SUB-ROUND cuts the     */
+/* next sphere of every cloud that still needs one.  Same layout as above (clouds back to back,     */
+/* HOST cloud_row_splits_host / active_host, at most 256 slots, kernel nodes only).                 */
+/* ml3d_sphere_select: for the a-th active slot s, centre = points[splits[s] + center_index[s]]:     */
+/*   the cloud-local indices of the cloud's points with d2 <= radius * radius, where                 */
+/*   d2 = ((dx*dx)+(dy*dy))+(dz*dz) in float32 without fma, ascending by (d2, index) -- bit for bit   */
+/*   the row ml3d_radius_count / _fill return for that ONE query on that cloud alone (what the host  */
+/*   loop's search_tree.query_radius is served by; the distance is shared in the source).  The lists */
+/*   lie back to back in out_index in the order of active_host; out_count[s] (DEVICE int32           */
+/*   [n_clouds], active slots only) is the length of slot s's list.  out_capacity: entries of        */
+/*   out_index, at least the points of the active clouds.  Possibilities are not touched.           */
+/*   Method: keys (item, d2 bits | all ones outside the sphere) of all active points, ONE stable     */
+/*   sort, the leading count[a] entries of every segment.                                            */
+/* ml3d_sphere_batch: the body of the loop of kpconv.py:446-531 for one sphere of each of the        */
+/*   n_active slots (two spheres of one cloud are never in one call).  Per item a (HOST arrays       */
+/*   indexed by a): cand + cand_offset_host[a] = its n_host[a] candidates (a list of                  */
+/*   ml3d_sphere_select), perm = DEVICE concatenation of the host's shuffles of 0..n_a-1, keep =     */
+/*   optional DEVICE concatenation of the host's choice(n_a, m_a) results for the items with         */
+/*   m_host[a] >= 0 (m_host[a] < 0: no cut), zero_extra_host[a] != 0: the colour drop.  In the      */
+/*   reference's order: picked = cand[perm]; d = float32 squared distances to the centre (three      */
+/*   squares added left to right); possibility[picked] += (double)(1 - d / max d)^2 (float32) over   */
+/*   ALL n_a points; sphere = p - centre; sphere[:, dims] -= mean[dims], mean = the SEQUENTIAL       */
+/*   float32 column sum over all n_a rows / n_a (as ml3d_patch_recenter); if `linear`:               */
+/*   extra[cloud rows] = (extra - feat_bias) / feat_scale IN PLACE over the WHOLE cloud              */
+/*   (transforms.py:18-22 on the cached features: once per sphere, cumulatively);                    */
+/*   columns = [sphere | extra[picked]]; rows keep of all of them; columns[:, 3:] *= 0 if            */
+/*   zero_extra (a product: -0.0 for a negative value, like numpy's).  Outputs back to back in item  */
+/*   order, item a with m_a (or n_a) rows: out_pts [M, 3], out_columns [M, 3 + n_extra], out_sel     */
+/*   (cloud-local), out_row (rows of the concatenated arrays).  The n_active sequential means run    */
+/*   side by side, one workgroup each.  Workspace: n_in = the sum of n_host.                         */
+size_t ml3d_sphere_select_workspace_bytes(int64_t n_points, int64_t n_active);
+
+int ml3d_sphere_select(const float* points, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                       const int32_t* active_host, int64_t n_active, const int32_t* center_index, float radius,
+                       int32_t* out_index, int64_t out_capacity, int32_t* out_count,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+size_t ml3d_sphere_batch_workspace_bytes(int64_t n_items, int64_t n_in);
+
+int ml3d_sphere_batch(const float* points, double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                      const int32_t* active_host, int64_t n_active, const int32_t* center_index, const int32_t* cand,
+                      const int64_t* cand_offset_host, const int32_t* n_host, const int32_t* perm, const int32_t* keep,
+                      const int32_t* m_host, const int32_t* zero_extra_host, int dims_mask, float* extra, int n_extra,
+                      float feat_bias, float feat_scale, int linear, float* out_pts, float* out_columns,
+                      int32_t* out_sel, int32_t* out_row, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- RandLA-Net random_sample as a differentiable op (training side, SURVEY.md §8 f4, ABI 5) ------------------ */
 /* ml3d_randla_gather_max: out[b, i, c] = max_k features[b, pool_idx[b, i, k], c], i < n_out (randlanet.py:300-327;   */
 /*   pool_idx = the level's WHOLE neighbour matrix [batch, n_in, 16] (batch-local indices): item b's pooling rows are  */

@@ -9,6 +9,10 @@
 //   ml3d_patch_batch          keys of all active points -> ONE 64-bit sort by distance -> one stable 8-bit pass by cloud ->
 //                             crop + distances + maxima -> possibility bump -> the A sequential means SIDE BY SIDE (one workgroup
 //                             per cloud) -> recentre + features
+// KPFCNN's input-sphere loop (kpconv.py:446-531) advances several clouds the same way, one SUB-ROUND per sphere:
+//   ml3d_sphere_select        keys (cloud, float32 d2 | all ones outside the radius) -> ONE sort -> the leading hits of every segment
+//   ml3d_sphere_batch         gather through the shuffle + distances + maxima -> possibility bump -> the sequential means side by side
+//                             -> in-place rescale of the clouds' cached colours -> recentre + columns + cut + colour drop
 // The clouds lie back to back in device arrays; their boundaries (cloud_row_splits) and the list of active slots are HOST arrays,
 // read during the call and carried to the kernels by value (PbItems): no upload, no allocation, kernel nodes only.
 #include <hip/hip_runtime.h>
@@ -183,6 +187,160 @@ pb_apply(float* __restrict__ pts, int64_t k, int dims_mask, const float* __restr
     for (int c = 0; c < n_extra; ++c) feats[o * C + 3 + c] = patch_feat_f32(ex[c], bias, scale);
 }
 
+// ---- the sphere loop of KPFCNN (kpconv.py:446-531 around semseg_spatially_regular.py:62-108) for several clouds -----------------------
+// ml3d_sphere_select: the radius query of every active cloud's centre as ONE sort.  Key of point i of item a = (a, bits of its
+// float32 distance) for a point inside the sphere, (a, all ones) for one outside: after the stable sort an item's hits stand first in
+// its segment, ascending in (d2, index) -- ml3d_radius_fill's row for that query (the same dist2_canon, the same d2 <= r * r).
+__global__ void __launch_bounds__(256)
+ss_keys(const float* __restrict__ pts, PbItems it, const int32_t* __restrict__ center_index, float r2, u64* __restrict__ keys,
+        uint32_t* __restrict__ vals, int* __restrict__ cnt) {
+    const int a = blockIdx.y;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if ((int)blockIdx.x * 256 >= it.len[a]) return;           // (uniform over the workgroup)
+    bool hit = false;
+    if (i < it.len[a]) {
+        const float* c = pb_center(pts, it, a, center_index);
+        const float* p = pts + 3 * ((int64_t)it.start[a] + i);
+        const float d2 = dist2_canon(c[0], c[1], c[2], p[0], p[1], p[2]);
+        hit = d2 <= r2;
+        const int64_t pos = (int64_t)it.cstart[a] + i;
+        keys[pos] = ((u64)(uint32_t)(it.first + a) << 32) | (u64)(hit ? __float_as_uint(d2) : 0xffffffffu);
+        vals[pos] = (uint32_t)pos;
+    }
+    const int n = __popcll(__ballot(hit));
+    if ((threadIdx.x & 63) == 0 && n) atomicAdd(cnt + it.first + a, n);
+}
+
+// the lists back to back in active order: item a's starts at the sum of the counts before it (at most 255 of them, summed per workgroup)
+__global__ void __launch_bounds__(256)
+ss_emit(const uint32_t* __restrict__ sorted, PbItems it, const int* __restrict__ cnt, int32_t* __restrict__ out_index,
+        int32_t* __restrict__ out_count) {
+    __shared__ int part[4];
+    const int a = blockIdx.y;
+    const int item = it.first + a;
+    const int n = cnt[item];
+    if (blockIdx.x == 0 && threadIdx.x == 0) out_count[it.slot[a]] = n;
+    if ((int)blockIdx.x * 256 >= n) return;                   // (uniform over the workgroup)
+    int v = (int)threadIdx.x < item ? cnt[threadIdx.x] : 0;   // item < PB_MAX_CLOUDS == 256 threads
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int64_t off = (int64_t)part[0] + part[1] + part[2] + part[3];
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j < n) out_index[off + j] = (int32_t)(sorted[(int64_t)it.cstart[a] + j] - (uint32_t)it.cstart[a]);
+}
+
+// ml3d_sphere_batch: the spheres of one call, by value in the kernel arguments (2.6 KB)
+struct SbItems {
+    int start[PB_ITEMS];       // first row of the sphere's cloud in the concatenated arrays
+    int len[PB_ITEMS];         // the cloud's number of points
+    int center[PB_ITEMS];      // slot of the cloud (index into center_index)
+    int cand[PB_ITEMS];        // first entry of the sphere's candidate list
+    int n[PB_ITEMS];           // its length = the sphere's points before the cut
+    int in0[PB_ITEMS];         // first entry of the sphere in perm and in the per-point scratch
+    int keep0[PB_ITEMS];       // first entry of its rows in keep; -1: no cut
+    int out0[PB_ITEMS];        // first output row
+    int m[PB_ITEMS];           // output rows
+    int zero[PB_ITEMS];        // columns 3.. of the output are multiplied by zero
+    int first;                 // ordinal of item 0 of this launch among the items of the call
+};
+
+__device__ __forceinline__ const float* sb_center(const float* __restrict__ pts, const SbItems& it, int a,
+                                                  const int32_t* __restrict__ center_index) {
+    int c = center_index[it.center[a]];
+    c = c < 0 ? 0 : (c >= it.len[a] ? it.len[a] - 1 : c);
+    return pts + 3 * ((int64_t)it.start[a] + c);
+}
+
+// picked = cand[perm]; distances to the centre and their maximum; sphere = p - centre (rows in the shuffle's order)
+__global__ void __launch_bounds__(256)
+sb_gather(const float* __restrict__ pts, SbItems it, const int32_t* __restrict__ center_index, const int32_t* __restrict__ cand,
+          const int32_t* __restrict__ perm, float* __restrict__ sph, int32_t* __restrict__ row_of, float* __restrict__ d2,
+          unsigned* __restrict__ d2max_bits) {
+    const int a = blockIdx.y;
+    const int n = it.n[a];
+    if ((int)blockIdx.x * 256 >= n) return;                   // (uniform over the workgroup)
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    float d = 0.f;
+    if (j < n) {
+        int q = perm[(int64_t)it.in0[a] + j];
+        q = q < 0 ? 0 : (q >= n ? n - 1 : q);                 // (a shuffle of 0..n-1; anything else is clamped, never followed)
+        int i = cand[(int64_t)it.cand[a] + q];
+        i = i < 0 ? 0 : (i >= it.len[a] ? it.len[a] - 1 : i);
+        const int64_t row = (int64_t)it.start[a] + i;
+        const float* c = sb_center(pts, it, a, center_index);
+        const float x = pts[3 * row], y = pts[3 * row + 1], z = pts[3 * row + 2];
+        const int64_t o = (int64_t)it.in0[a] + j;
+        d = patch_d2_f32(x, y, z, c);
+        d2[o] = d;
+        row_of[o] = (int32_t)row;
+        sph[3 * o] = __fsub_rn(x, c[0]); sph[3 * o + 1] = __fsub_rn(y, c[1]); sph[3 * o + 2] = __fsub_rn(z, c[2]);
+    }
+    unsigned b = __float_as_uint(d);                          // max of non-negative floats == max of their bit patterns
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(d2max_bits + it.first + a, b);
+}
+
+__global__ void __launch_bounds__(256)
+sb_bump(SbItems it, const int32_t* __restrict__ row_of, const float* __restrict__ d2, const unsigned* __restrict__ d2max_bits,
+        double* __restrict__ possibility) {
+    const int a = blockIdx.y;
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j >= it.n[a]) return;
+    const int64_t o = (int64_t)it.in0[a] + j;
+    possibility[row_of[o]] += (double)patch_bump_f32(d2[o], __uint_as_float(d2max_bits[it.first + a]));
+}
+
+// the sequential column sums of the spheres side by side: one workgroup per item
+__global__ void __launch_bounds__(256)
+sb_mean_seq(const float* __restrict__ sph, SbItems it, float* __restrict__ mean) {
+    const int a = blockIdx.x;
+    patch_mean_seq_body(sph + 3 * (int64_t)it.in0[a], it.n[a], mean + 4 * (int64_t)(it.first + a));
+}
+
+// trans_normalize's 'linear' rescale of the cloud's CACHED features, in place, once per sphere (kpconv.py:500-503 through
+// transforms.py:18-22: the reference renormalises the cached array every time, cumulatively)
+__global__ void __launch_bounds__(256)
+sb_rescale(float* __restrict__ extra, SbItems it, int n_extra, float bias, float scale) {
+    const int a = blockIdx.y;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (int64_t)it.len[a] * n_extra) return;
+    float* p = extra + (int64_t)it.start[a] * n_extra + e;
+    *p = patch_feat_f32(*p, bias, scale);
+}
+
+// recentre on the mean, columns = [sphere | extra[picked]], the cut (rows keep), the colour drop
+__global__ void __launch_bounds__(256)
+sb_emit(SbItems it, const float* __restrict__ sph, const int32_t* __restrict__ row_of, const float* __restrict__ mean,
+        const int32_t* __restrict__ keep, int dims_mask, const float* __restrict__ extra, int n_extra, float* __restrict__ out_pts,
+        float* __restrict__ out_columns, int32_t* __restrict__ out_sel, int32_t* __restrict__ out_row) {
+    const int a = blockIdx.y;
+    const int jo = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (jo >= it.m[a]) return;
+    int j = jo;
+    if (it.keep0[a] >= 0) {
+        j = keep[(int64_t)it.keep0[a] + jo];
+        j = j < 0 ? 0 : (j >= it.n[a] ? it.n[a] - 1 : j);
+    }
+    const int64_t i = (int64_t)it.in0[a] + j, o = (int64_t)it.out0[a] + jo;
+    const int C = 3 + n_extra;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        float v = sph[3 * i + d];
+        if (dims_mask & (1 << d)) v = __fsub_rn(v, mean[4 * (int64_t)(it.first + a) + d]);
+        out_pts[3 * o + d] = v;
+        out_columns[o * C + d] = v;
+    }
+    const int32_t row = row_of[i];
+    for (int c = 0; c < n_extra; ++c) {
+        const float v = extra[(int64_t)row * n_extra + c];
+        out_columns[o * C + 3 + c] = it.zero[a] ? __fmul_rn(v, 0.f) : v;      // columns[:, 3:] *= 0 (kpconv.py:526-527)
+    }
+    out_sel[o] = row - it.start[a];
+    out_row[o] = row;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 static inline size_t pb_al(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -322,5 +480,124 @@ extern "C" int ml3d_patch_batch(const float* points, double* possibility, const 
     if (dims_mask) hipLaunchKernelGGL(pb_mean_seq, dim3((unsigned)n_active), dim3(256), 0, st, out_pts, k, mean);
     hipLaunchKernelGGL(pb_apply, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_pts, k, dims_mask, mean, out_row, extra, n_extra,
                        feat_bias, feat_scale, out_features);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" size_t ml3d_sphere_select_workspace_bytes(int64_t n_points, int64_t n_active) {
+    if (n_points < 0 || n_active < 0) return 0;
+    const int64_t m = n_points > 0 ? n_points : 1;
+    return pb_al(4 * (size_t)(n_active > 0 ? n_active : 1)) + pb_al(sizeof(u64) * (size_t)m) + pb_al(sizeof(uint32_t) * (size_t)m) +
+           sort_ws_bytes(m) + 512;
+}
+
+extern "C" int ml3d_sphere_select(const float* points, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                                  const int32_t* active_host, int64_t n_active, const int32_t* center_index, float radius,
+                                  int32_t* out_index, int64_t out_capacity, int32_t* out_count, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    if (!(radius >= 0.f)) return ML3D_E_INVALID;
+    const int64_t m = pb_check(cloud_row_splits_host, n_clouds, active_host, n_active, 1);
+    if (m < 0 || !points || !center_index || !out_index || !out_count || !workspace || out_capacity < m) return ML3D_E_INVALID;
+    if (workspace_bytes < ml3d_sphere_select_workspace_bytes(m, n_active)) return ML3D_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* p = ws_align(workspace);
+    int* cnt = (int*)p;               p += pb_al(4 * (size_t)n_active);       // [n_active]  hits per item
+    u64* keys = (u64*)p;              p += pb_al(sizeof(u64) * (size_t)m);
+    uint32_t* vals = (uint32_t*)p;    p += pb_al(sizeof(uint32_t) * (size_t)m);
+    SortWs sw;
+    if (!sort_ws_carve(p, sort_ws_bytes(m), m, &sw)) return ML3D_E_WORKSPACE;
+    zero_async(cnt, pb_al(4 * (size_t)n_active), st);
+    const float r2 = radius * radius;                                        // (ml3d_radius_fill's own bound)
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        int longest;
+        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+        hipLaunchKernelGGL(ss_keys, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, points, it, center_index,
+                           r2, keys, vals, cnt);
+    }
+    if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
+    int bits = 32;
+    while ((1ll << (bits - 32)) < n_active) ++bits;
+    if (sort_pairs_u64(keys, vals, m, bits, sw, st, true)) return ML3D_E_LAUNCH;
+    const uint32_t* sorted = sort_result_in_alt(m, bits) ? sw.vals_alt : vals;
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        int longest;
+        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+        hipLaunchKernelGGL(ss_emit, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, sorted, it, cnt, out_index,
+                           out_count);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" size_t ml3d_sphere_batch_workspace_bytes(int64_t n_items, int64_t n_in) {
+    if (n_items < 0 || n_in < 0) return 0;
+    const size_t a = (size_t)(n_items > 0 ? n_items : 1), n = (size_t)(n_in > 0 ? n_in : 1);
+    return pb_al(4 * a) + pb_al(16 * a) + pb_al(12 * n) + 2 * pb_al(4 * n) + 512;
+}
+
+extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
+                                 const int32_t* active_host, int64_t n_active, const int32_t* center_index, const int32_t* cand,
+                                 const int64_t* cand_offset_host, const int32_t* n_host, const int32_t* perm, const int32_t* keep,
+                                 const int32_t* m_host, const int32_t* zero_extra_host, int dims_mask, float* extra, int n_extra,
+                                 float feat_bias, float feat_scale, int linear, float* out_pts, float* out_columns, int32_t* out_sel,
+                                 int32_t* out_row, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_extra < 0 || (n_extra > 0 && !extra) || (dims_mask & ~7) || !cand_offset_host || !n_host || !zero_extra_host ||
+        (keep && !m_host))
+        return ML3D_E_INVALID;
+    if (pb_check(cloud_row_splits_host, n_clouds, active_host, n_active, 1) < 0) return ML3D_E_INVALID;
+    if (!points || !possibility || !center_index || !cand || !perm || !out_pts || !out_columns || !out_sel || !out_row || !workspace)
+        return ML3D_E_INVALID;
+    int64_t n_in = 0, n_out = 0;
+    for (int64_t a = 0; a < n_active; ++a) {
+        const int64_t s = active_host[a], len = cloud_row_splits_host[s + 1] - cloud_row_splits_host[s];
+        const int64_t n = n_host[a], m = keep && m_host[a] >= 0 ? m_host[a] : n;
+        if (n < 1 || n > len || m < 1 || m > n || cand_offset_host[a] < 0 || cand_offset_host[a] + n > 0x7ffffff0ll) return ML3D_E_INVALID;
+        n_in += n;
+        n_out += m;
+    }
+    if (n_in > 0x7ffffff0ll) return ML3D_E_INVALID;
+    if (workspace_bytes < ml3d_sphere_batch_workspace_bytes(n_active, n_in)) return ML3D_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    char* p = ws_align(workspace);
+    unsigned* mx = (unsigned*)p;      p += pb_al(4 * (size_t)n_active);       // [n_active]     bits of the largest float32 distance
+    float* mean = (float*)p;          p += pb_al(16 * (size_t)n_active);      // [n_active][4]  column means
+    float* sph = (float*)p;           p += pb_al(12 * (size_t)n_in);          // [n_in][3]      p - centre, in the shuffle's order
+    float* d2 = (float*)p;            p += pb_al(4 * (size_t)n_in);
+    int32_t* row_of = (int32_t*)p;
+    zero_async(mx, pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active), st);
+    int64_t in0 = 0, keep0 = 0, out0 = 0;
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        SbItems it;
+        int max_n = 0, max_m = 0, max_len = 0;
+        for (int a = 0; a < PB_ITEMS; ++a) {
+            const bool live = a < count;
+            const int64_t s = live ? active_host[first + a] : 0;
+            const int64_t n = live ? n_host[first + a] : 0;
+            const bool cut = live && keep && m_host[first + a] >= 0;
+            const int64_t m = cut ? m_host[first + a] : n;
+            it.start[a] = live ? (int)cloud_row_splits_host[s] : 0;
+            it.len[a] = live ? (int)(cloud_row_splits_host[s + 1] - cloud_row_splits_host[s]) : 0;
+            it.center[a] = (int)s;
+            it.cand[a] = live ? (int)cand_offset_host[first + a] : 0;
+            it.n[a] = (int)n; it.in0[a] = (int)in0; it.keep0[a] = cut ? (int)keep0 : -1; it.out0[a] = (int)out0; it.m[a] = (int)m;
+            it.zero[a] = live && zero_extra_host[first + a] ? 1 : 0;
+            in0 += n; out0 += m;
+            if (cut) keep0 += m;
+            if (n > max_n) max_n = (int)n;
+            if (m > max_m) max_m = (int)m;
+            if (it.len[a] > max_len) max_len = it.len[a];
+        }
+        it.first = (int)first;
+        const dim3 gn((unsigned)((max_n + 255) / 256), (unsigned)count), gm((unsigned)((max_m + 255) / 256), (unsigned)count);
+        hipLaunchKernelGGL(sb_gather, gn, dim3(256), 0, st, points, it, center_index, cand, perm, sph, row_of, d2, mx);
+        hipLaunchKernelGGL(sb_bump, gn, dim3(256), 0, st, it, row_of, d2, mx, possibility);
+        if (dims_mask) hipLaunchKernelGGL(sb_mean_seq, dim3((unsigned)count), dim3(256), 0, st, sph, it, mean);
+        if (linear && n_extra)
+            hipLaunchKernelGGL(sb_rescale, dim3((unsigned)(((int64_t)max_len * n_extra + 255) / 256), (unsigned)count), dim3(256), 0, st,
+                               extra, it, n_extra, feat_bias, feat_scale);
+        hipLaunchKernelGGL(sb_emit, gm, dim3(256), 0, st, it, sph, row_of, mean, keep, dims_mask, extra, n_extra, out_pts, out_columns,
+                           out_sel, out_row);
+    }
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

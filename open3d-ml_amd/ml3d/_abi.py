@@ -74,6 +74,7 @@ SYMBOLS = [
     "ml3d_patch_crop",
     "ml3d_patch_recenter",
     "ml3d_possibility_argmin_workspace_bytes", "ml3d_possibility_argmin", "ml3d_patch_batch_workspace_bytes", "ml3d_patch_batch",
+    "ml3d_sphere_select_workspace_bytes", "ml3d_sphere_select", "ml3d_sphere_batch_workspace_bytes", "ml3d_sphere_batch",
     "ml3d_vote_update",
     "ml3d_randla_gather_max",
     "ml3d_randla_gather_max_backward",
@@ -258,6 +259,15 @@ def bind(lib):
     lib.ml3d_patch_batch_workspace_bytes.argtypes = [i64, i64, i64]
     lib.ml3d_patch_batch.restype = C.c_int
     lib.ml3d_patch_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, i64, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
+    lib.ml3d_sphere_select_workspace_bytes.restype = sz
+    lib.ml3d_sphere_select_workspace_bytes.argtypes = [i64, i64]
+    lib.ml3d_sphere_select.restype = C.c_int
+    lib.ml3d_sphere_select.argtypes = [vp, vp, i64, vp, i64, vp, f32, vp, i64, vp, vp, sz, vp]
+    lib.ml3d_sphere_batch_workspace_bytes.restype = sz
+    lib.ml3d_sphere_batch_workspace_bytes.argtypes = [i64, i64]
+    lib.ml3d_sphere_batch.restype = C.c_int
+    lib.ml3d_sphere_batch.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, i32, vp, vp, vp, vp,
+                                      vp, sz, vp]
     lib.ml3d_randla_gather_max.restype = C.c_int
     lib.ml3d_randla_gather_max.argtypes = [vp, vp, i64, i64, i64, i32, vp, vp]
     lib.ml3d_randla_gather_max_backward.restype = C.c_int

@@ -191,6 +191,111 @@ def device_patch_batch(points, possibility, cloud_row_splits, active, center_ind
     return pts, feats, sel, row
 
 
+def sphere_select(points, cloud_row_splits, active, center_index, radius, out=None):
+    """The radius query of the sphere sampler (semseg_spatially_regular.py:86-87) for the active clouds of a concatenated set in ONE
+    call: per active slot s the cloud-local indices of its points within ``radius`` of ``points[splits[s] + center_index[s]]``,
+    ascending (d2, index) -- the row ``fixed_radius_search`` returns for that one query on that cloud alone.  ``points`` float32
+    [N, 3], HOST ``cloud_row_splits`` [C + 1] and HOST ``active`` (None: all), ``center_index`` DEVICE int32 [C].  Returns
+    (indices int32 [points of the active clouds]: the lists back to back in active order, counts DEVICE int32 [C]: written for the
+    active slots only) -- nothing is read back; the counts are the caller's one read-back.  ``out``: the two preallocated."""
+    lib = _abi.get()
+    _need_gpu(points, center_index)
+    splits, act = _host_splits(cloud_row_splits, active, "sphere_select")
+    n_clouds = splits.size - 1
+    dev = points.device
+    n = int(splits[-1])
+    m = int(np.diff(splits)[act].sum())
+    if points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3) or center_index.dtype != torch.int32 or \
+            center_index.numel() != n_clouds or not center_index.is_contiguous() or not float(radius) >= 0 or np.any(np.diff(splits)[act] < 1):
+        raise RuntimeError("sphere_select: float32 [N, 3] points, N == cloud_row_splits[-1], int32 [C] centre indices, radius >= 0, "
+                           "no empty active cloud")
+    if out is None:
+        idx = torch.empty(m, dtype=torch.int32, device=dev)
+        cnt = torch.empty(n_clouds, dtype=torch.int32, device=dev)
+    else:
+        idx, cnt = out
+        if idx.dtype != torch.int32 or cnt.dtype != torch.int32 or idx.numel() < m or cnt.numel() != n_clouds or \
+                not (idx.is_contiguous() and cnt.is_contiguous()):
+            raise RuntimeError("sphere_select: out = (int32 [>= points of the active clouds], int32 [C]), contiguous")
+        _need_gpu(idx, cnt)
+    wsb = lib.ml3d_sphere_select_workspace_bytes(m, act.size)
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_sphere_select(points.data_ptr(), splits.ctypes.data, n_clouds, act.ctypes.data, act.size, center_index.data_ptr(),
+                                    float(radius), idx.data_ptr(), idx.numel(), cnt.data_ptr(), ws.data_ptr(), wsb, _stream())
+    _abi.check(rc, "ml3d_sphere_select")
+    return idx, cnt
+
+
+def device_sphere_batch(points, possibility, cloud_row_splits, active, center_index, cand, cand_offsets, counts, perm, keep=None,
+                        keep_counts=None, zero_extra=None, recenter_dims=(0, 1, 2), extra=None, feat_bias=0.0, feat_scale=1.0,
+                        linear=False):
+    """One input sphere of each of the A active clouds (the body of the loop of kpconv.py:446-531 after the radius query), nothing
+    read back: ``cand`` DEVICE int32 (lists of ``sphere_select``), HOST ``cand_offsets`` [A] / ``counts`` [A] (first entry and
+    length n_a of item a's list), ``perm`` DEVICE int32 [sum n_a] (the host's shuffles of 0..n_a-1, concatenated), ``keep`` optional
+    DEVICE int32 (the host's ``choice(n_a, m_a, replace=False)`` results of the items with HOST ``keep_counts[a]`` >= 0,
+    concatenated; < 0: the item is not cut), HOST ``zero_extra`` [A] flags (the colour drop).  ``possibility`` float64 [N] is bumped
+    IN PLACE over all n_a points; with ``linear`` the WHOLE cloud's rows of ``extra`` float32 [N, c] are rescaled IN PLACE
+    ((extra - feat_bias) / feat_scale, once per call, like the reference on its cached features).  Returns (points [M, 3]
+    recentred on ``recenter_dims``, columns [M, 3 + c], cloud-local indices int32 [M], rows of the concatenated arrays int32 [M],
+    HOST output offsets int64 [A + 1]) -- item a's rows are [offsets[a], offsets[a + 1])."""
+    lib = _abi.get()
+    _need_gpu(points, possibility, center_index, cand, perm)
+    splits, act = _host_splits(cloud_row_splits, active, "device_sphere_batch")
+    n_clouds, A = splits.size - 1, int(act.size)
+    dev = points.device
+    n = int(splits[-1])
+    offs = np.ascontiguousarray(cand_offsets, dtype=np.int64).reshape(-1)
+    n_a = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    lens = np.diff(splits)[act]
+    if points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3) or possibility.dtype != torch.float64 or \
+            not possibility.is_contiguous() or possibility.numel() != n or center_index.dtype != torch.int32 or \
+            center_index.numel() != n_clouds or not center_index.is_contiguous() or cand.dtype != torch.int32 or not cand.is_contiguous() or \
+            perm.dtype != torch.int32 or not perm.is_contiguous() or offs.size != A or n_a.size != A or np.any(n_a < 1) or \
+            np.any(n_a > lens) or np.any(offs < 0) or np.any(offs + n_a > cand.numel()) or perm.numel() != int(n_a.sum()):
+        raise RuntimeError("device_sphere_batch: float32 [N, 3] points, float64 [N] possibilities, N == cloud_row_splits[-1], int32 [C] "
+                           "centre indices, int32 candidates holding every item's list, 1 <= n_a <= the cloud's size, int32 [sum n_a] shuffles")
+    m_a = None
+    out_n = n_a.astype(np.int64)
+    if keep is not None:
+        _need_gpu(keep)
+        m_a = np.ascontiguousarray(keep_counts, dtype=np.int32).reshape(-1)
+        if keep.dtype != torch.int32 or not keep.is_contiguous() or m_a.size != A or np.any(m_a == 0) or np.any(m_a > n_a) or \
+                keep.numel() != int(m_a[m_a > 0].sum()):
+            raise RuntimeError("device_sphere_batch: keep = int32 [sum of the m_a >= 1], 1 <= m_a <= n_a (or < 0: no cut)")
+        out_n = np.where(m_a > 0, m_a, n_a).astype(np.int64)
+    zero = np.zeros(A, np.int32) if zero_extra is None else np.ascontiguousarray(zero_extra).astype(np.int32).reshape(-1)
+    if zero.size != A:
+        raise RuntimeError("device_sphere_batch: one zero_extra flag per item")
+    n_extra = 0
+    if extra is not None:
+        if extra.dtype != torch.float32 or not extra.is_contiguous() or extra.dim() != 2 or extra.shape[0] != n:
+            raise RuntimeError("device_sphere_batch: extra must be a contiguous float32 [N, c] tensor")
+        _need_gpu(extra)
+        n_extra = int(extra.shape[1])
+    out_offsets = np.zeros(A + 1, np.int64)
+    np.cumsum(out_n, out=out_offsets[1:])
+    M = int(out_offsets[-1])
+    pts = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    cols = torch.empty((M, 3 + n_extra), dtype=torch.float32, device=dev)
+    sel = torch.empty(M, dtype=torch.int32, device=dev)
+    row = torch.empty(M, dtype=torch.int32, device=dev)
+    mask = 0
+    for d in recenter_dims:
+        mask |= 1 << int(d)
+    wsb = lib.ml3d_sphere_batch_workspace_bytes(A, int(n_a.sum()))
+    ws = _ws(wsb, dev)
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_sphere_batch(points.data_ptr(), possibility.data_ptr(), splits.ctypes.data, n_clouds, act.ctypes.data, A,
+                                   center_index.data_ptr(), cand.data_ptr(), offs.ctypes.data, n_a.ctypes.data, perm.data_ptr(),
+                                   None if keep is None else keep.data_ptr(), None if m_a is None else m_a.ctypes.data, zero.ctypes.data,
+                                   mask, None if extra is None else extra.data_ptr(), n_extra, float(feat_bias), float(feat_scale),
+                                   1 if linear else 0, pts.data_ptr(), cols.data_ptr(), sel.data_ptr(), row.data_ptr(), ws.data_ptr(), wsb,
+                                   _stream())
+    _abi.check(rc, "ml3d_sphere_batch")
+    return pts, cols, sel, row, out_offsets
+
+
 def argmax_labels(scores, out=None):
     """uint8 labels [...] = argmax over the last axis of float32 ``scores`` [..., C <= 256] (first maximum, like
     torch.argmax) -- one pass over the scores instead of torch's generic reduction + dtype cast."""

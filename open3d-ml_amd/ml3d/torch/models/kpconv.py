@@ -380,6 +380,8 @@ class KPFCNN(nn.Module):
         pts = [t.to(dev, torch.float32).contiguous() for t in batch.points]
         idx = lambda lst: [t.to(dev).to(torch.int32).contiguous() for t in lst]
         nbrs, pools, ups = idx(batch.neighbors), idx(batch.pools), idx(batch.upsamples)
+        # (inference_many: the max-pool's own copy of the pool matrices, see _pools_of_own_batches; None everywhere else)
+        pools_max = getattr(batch, 'pools_max', None)
         x = batch.features.to(dev, torch.float32).contiguous()
         skip_x = []
         for bi, (blk, p) in enumerate(zip(self.encoder_blocks, P['enc'])):
@@ -409,7 +411,7 @@ class KPFCNN(nn.Module):
             else:
                 y = x if p['u1'] is None else self._unary(p['u1'], x)
                 y = conv(y)
-                sc = ops.gather_pool(x, inds, 'max') if strided else x
+                sc = ops.gather_pool(x, inds if pools_max is None else pools_max[L], 'max') if strided else x
                 if p['u2sc'] is not None:
                     x = self._unary(p['u2sc'], y, a2=sc, act=1, slope=lr)
                     continue
@@ -617,29 +619,31 @@ class KPFCNN(nn.Module):
                                        proj_splits=("test", "testing", "validation", "valid"),
                                        host_index=self.cfg.get('sampler_index', 'gpu') == 'sklearn')
 
-    def _draw_augmentation(self, n, dim):
+    def _draw_augmentation(self, n, dim, rng=None):
         """The np.random draws of the reference's augmentation (kpconv.py:647-712), in its order -- rotation angle(s), scale,
         symmetry flips, per-point noise -- so that a seeded run consumes the generator exactly like the reference does.
-        Returns (R [dim, dim] f32, scale [dim] f32, noise [n, dim] f32)."""
+        Returns (R [dim, dim] f32, scale [dim] f32, noise [n, dim] f32).  ``rng``: a ``np.random.RandomState`` to draw from instead
+        of the global one (``inference_many``: one generator per cloud)."""
+        rng = np.random if rng is None else rng
         cfg, two_pi = self.cfg, 2 * np.pi
         R = np.eye(dim)
         if dim == 3 and cfg.augment_rotation == 'vertical':
-            a = np.random.rand() * two_pi
+            a = rng.rand() * two_pi
             R = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]], dtype=np.float32)
         elif dim == 3 and cfg.augment_rotation == 'all':
             from ._datapath import create_3D_rotations
-            a = np.random.rand() * two_pi
-            b = (np.random.rand() - 0.5) * np.pi
+            a = rng.rand() * two_pi
+            b = (rng.rand() - 0.5) * np.pi
             axis = np.array([np.cos(a) * np.cos(b), np.sin(a) * np.cos(b), np.sin(b)])
-            R = create_3D_rotations(axis.reshape(1, -1), (np.random.rand() * two_pi).reshape(1, -1))[0]
+            R = create_3D_rotations(axis.reshape(1, -1), (rng.rand() * two_pi).reshape(1, -1))[0]
         lo, hi = cfg.augment_scale_min, cfg.augment_scale_max
         if cfg.augment_scale_anisotropic:
-            scale = np.random.rand(dim) * (hi - lo) + lo
+            scale = rng.rand(dim) * (hi - lo) + lo
         else:
-            scale = np.random.rand() * (hi - lo) - lo          # sic: the reference subtracts min (kpconv.py:701)
-        flips = np.array(cfg.augment_symmetries).astype(np.int32) * np.random.randint(2, size=dim)
+            scale = rng.rand() * (hi - lo) - lo          # sic: the reference subtracts min (kpconv.py:701)
+        flips = np.array(cfg.augment_symmetries).astype(np.int32) * rng.randint(2, size=dim)
         scale = (scale * (1 - flips * 2)).astype(np.float32)
-        noise = (np.random.randn(n, dim) * cfg.augment_noise).astype(np.float32)
+        noise = (rng.randn(n, dim) * cfg.augment_noise).astype(np.float32)
         return R.astype(np.float32), scale, noise
 
     def augmentation_transform(self, points, normals=None, verbose=False, is_test=False):
@@ -742,8 +746,10 @@ class KPFCNN(nn.Module):
         if getattr(self, 'trans_point_sampler', None) is None:
             self.trans_point_sampler = self._possibility_sampler
 
-    def _possibility_sampler(self, pc, feat, label, search_tree, num_points, radius=None):
-        """Radius-based spatially regular sampler on ``self.possibility`` (semseg_spatially_regular.py:62-108)."""
+    def _possibility_sampler(self, pc, feat, label, search_tree, num_points, radius=None, rng=None):
+        """Radius-based spatially regular sampler on ``self.possibility`` (semseg_spatially_regular.py:62-108).  ``rng``: the
+        generator of the shuffle (default: the ``np.random`` module)."""
+        rng = np.random if rng is None else rng
         n = 0
         while n < 2:
             center_id = int(np.argmin(self.possibility))
@@ -752,7 +758,7 @@ class KPFCNN(nn.Module):
             n = len(idxs)
             if n < 2:
                 self.possibility[center_id] += 0.001
-        idxs = np.random.permutation(idxs)
+        idxs = rng.permutation(idxs)
         pc = pc[idxs]
         dists = np.sum(np.square((pc - center_point).astype(np.float32)), axis=1)
         self.possibility[idxs] += np.square(1 - dists / np.max(dists))
@@ -772,6 +778,323 @@ class KPFCNN(nn.Module):
             self.inference_result = {'predict_labels': pred_labels, 'predict_scores': probs[self.inference_proj_inds]}
             return True
         return False
+
+    # ---- several clouds in flight: the next sphere of EVERY cloud that needs one per sub-round, one forward over all their batches ----
+    # The loop above runs on the host, one sphere at a time: np.argmin over a host array, a single-query radius search with a ragged
+    # read-back, the crop in numpy, an upload, and a forward over the two or three spheres of one cloud.  A cloud's spheres depend
+    # only on its own possibilities and its own random draws -- never on a logit -- so C clouds can advance together and each still
+    # produces exactly the spheres, batches and possibilities it produces alone (tests/kpconv_multicloud_cases.py).
+    @staticmethod
+    def _device_input_features(columns, in_features_dim):
+        """``dataloaders.kpconv_input_features`` on the device columns [xyz | feat] (column copies: the same bits)."""
+        ones = torch.ones((columns.shape[0], 1), dtype=torch.float32, device=columns.device)
+        d = int(in_features_dim)
+        if d == 1:
+            return ones
+        if d in (3, 5, 6) or d > 6:
+            assert columns.shape[1] > 3, "feat from dataset can not be None or try to set in_features_dim = 1, 2, 4"
+        if d == 5:
+            assert columns.shape[1] >= 6, "feat from dataset should have at least 3 dims, or try to set in_features_dim = 1, 2, 4"
+        if d < 1:
+            raise ValueError('in_features_dim should be >= 0')
+        cols = {2: columns[:, 2:3], 3: columns[:, 2:4], 4: columns[:, :3], 5: columns[:, 2:6]}.get(d, columns)
+        return torch.cat([ones, cols], 1).contiguous()
+
+    @staticmethod
+    def _pools_of_own_batches(batch, spheres_per_cloud):
+        """The pool matrices as the max-pool of each cloud's OWN batch sees them.  ``max_pool`` (kpconv.py:840-858) lets the zero
+        feature row of the shadow neighbour take part in the maximum, so a strided block's shortcut depends on whether a pooling
+        row is shorter than the matrix -- and the matrix is as wide as the longest row of the WHOLE batch.  In a cloud's own batch
+        its longest rows have no shadow entry; here they get some whenever another cloud has a longer row, and the logits of the
+        cloud's spheres would move (by 0.1 at |logits| of 4 in a forward over 13 spheres).  So for the max-pool only, a row as long
+        as the longest of its cloud has its shadow entries replaced by its first neighbour (a repeat changes no maximum); every
+        other row keeps its shadow entries, as in the cloud's own batch.  The convolutions keep the unchanged matrices (a
+        shadow neighbour adds zero to their sums).  Device ops only: the lengths are host knowledge."""
+        out = []
+        for l, mat in enumerate(batch.pools):
+            if mat.shape[0] == 0 or l + 1 >= len(batch.lengths):
+                out.append(mat)
+                continue
+            lens = [int(v) for v in batch.lengths[l + 1]]
+            rows, at = [], 0
+            for n_sph in spheres_per_cloud:
+                rows.append(sum(lens[at:at + n_sph]))
+                at += n_sph
+            dev = mat.device
+            cloud = torch.repeat_interleave(torch.arange(len(rows), device=dev), torch.as_tensor(rows, device=dev), output_size=sum(rows))
+            shadow = mat >= batch.points[l].shape[0]
+            length = (~shadow).sum(1)
+            longest = torch.zeros(len(rows), dtype=length.dtype, device=dev).scatter_reduce_(0, cloud, length, 'amax', include_self=True)
+            full = (length == longest[cloud]) & (length > 0)
+            out.append(torch.where(shadow & full[:, None], mat[:, :1], mat).contiguous())
+        return out
+
+    def _single_cloud_run(self, cloud, seed):
+        """The single-cloud loop to completion under ``np.random.seed(seed)``; the global generator's state is put back."""
+        state = np.random.get_state()
+        try:
+            np.random.seed(seed)
+            self.inference_begin(cloud)
+            batches = spheres = 0
+            while True:
+                inp = self.inference_preprocess()
+                batches += 1
+                spheres += len(inp['data'].lengths[0])
+                if self.inference_end(inp, self(inp['data'])):
+                    break
+            return self.inference_result, dict(num_batches=batches, num_spheres=spheres, retries=None,
+                                               possibility=np.array(self.possibility, dtype=np.float64))
+        finally:
+            np.random.set_state(state)
+
+    def inference_many(self, clouds, seeds=None, max_in_flight=8, on_batch=None):
+        """Segment a list of raw clouds (dicts as ``inference_begin`` takes) with up to ``max_in_flight`` of them advancing in lock
+        step.  One SUB-ROUND cuts the next input sphere of every cloud whose batch is not complete: one ``ops.possibility_argmin``,
+        one ``ops.sphere_select``, ONE read-back (the sphere sizes and, for clouds at a batch boundary, the minima of the finished
+        test), the host's draws uploaded in one pinned copy, one ``ops.device_sphere_batch``.  When every cloud's batch is complete:
+        one ``KPConvBatch`` over the device tensors of all spheres, one forward, one ``ops.vote_update`` per sphere ordinal into a
+        concatenated float16 accumulator.  Returns ``[{'predict_labels', 'predict_scores'}, ...]`` in input order.
+
+        Cloud i owns ``np.random.RandomState(seeds[i])`` (``seeds=None``: drawn from ``np.random``) and consumes it draw for draw
+        like ``np.random.seed(seeds[i])`` + the single-cloud loop (``inference_begin``, then ``inference_preprocess`` -> forward ->
+        ``inference_end``) does: the possibilities, per sphere the shuffle, the cut, the augmentation's draws and the colour drop, per
+        batch the grid rotations -- so its spheres, batches and final possibilities are that run's.
+        ``on_batch(spheres, batch, logits)`` is called after every forward: ``spheres[j]`` = (cloud, batch ordinal, sphere ordinal) of
+        the j-th sphere of ``batch``.  ``self.inference_many_info[i]``: ``num_batches``, ``num_spheres``, ``retries`` (centres whose
+        sphere held fewer than 2 points) and the final ``possibility`` (numpy float64).
+        The single-cloud loop serves, one cloud after the other: every cloud when the sampler is not this class's device one
+        (``sampler_index='sklearn'``, a user-set ``trans_point_sampler``) or ``t_normalize.normalize_points`` is on (its whole-array
+        ``mean()`` is a pairwise sum), and a cloud with fewer than 2 points after preprocessing."""
+        import time
+        cfg, dev = self.cfg, self.device
+        _abi.require_gpu(dev, "KPFCNN.inference_many")
+        if self.training:
+            raise RuntimeError("KPFCNN.inference_many: call model.eval() first")
+        n_clouds, S = len(clouds), int(max_in_flight)
+        if S < 1 or S > 256:
+            raise ValueError("KPFCNN.inference_many: 1 <= max_in_flight <= 256")
+        if seeds is None:
+            seeds = [int(v) for v in np.random.randint(0, 2 ** 31 - 1, size=n_clouds)]
+        if len(seeds) != n_clouds:
+            raise ValueError("KPFCNN.inference_many: one seed per cloud")
+        norm = cfg.get('t_normalize', {})
+        method = norm.get('method', None)
+        axes = [int(a) for a in norm.get('recentering', [0, 1, 2])]
+        linear = method == 'linear'
+        bias, scale = float(norm.get('feat_bias', 0)), float(norm.get('feat_scale', 1))
+        sampler = getattr(self, 'trans_point_sampler', None)
+        host_only = cfg.get('sampler_index', 'gpu') == 'sklearn' or (sampler is not None and sampler != self._possibility_sampler) or \
+            (linear and norm.get('normalize_points', False))
+        results = [None] * n_clouds
+        info = self.inference_many_info = [None] * n_clouds
+        stats = self.inference_many_stats = dict(read_backs=0, sub_rounds=0, forwards=0, host_draw_seconds=0.0)
+        self.test_smooth = 0.95
+        cap = min(cfg.batch_limit, cfg.max_in_points)
+        want = min(cfg.get('min_in_points', 3), cfg.max_in_points)
+        if want > cap:
+            raise ValueError("KPFCNN.inference_many: min_in_points exceeds batch_limit")
+        n_pool = 0                       # grid orientations a batch draws: one set per pooling layer (KPConvBatch)
+        for block in cfg.architecture:
+            if 'upsample' in block or 'global' in block:
+                break
+            n_pool += 'pool' in block or 'strided' in block
+        width = lambda c: 0 if (method == 'coords_only' or c.get('feat') is None) else int(np.asarray(c['feat']).shape[1])
+        groups = {}                      # clouds of one feature width share the concatenated arrays
+        host_path = list(range(n_clouds)) if host_only else []
+        if not host_only:
+            for i, c in enumerate(clouds):
+                groups.setdefault(width(c), []).append(i)
+        for n_extra, members in groups.items():
+            self._many_device_loop(clouds, seeds, members, n_extra, S, on_batch, results, info, stats, host_path,
+                                   dict(cap=cap, want=want, n_pool=n_pool, axes=axes, linear=linear, bias=bias, scale=scale), time)
+        for i in sorted(host_path):
+            results[i], info[i] = self._single_cloud_run(clouds[i], seeds[i])
+        return results
+
+    def _many_device_loop(self, clouds, seeds, members, n_extra, S, on_batch, results, info, stats, host_path, k, time):
+        """``inference_many`` for the clouds ``members`` (one feature width); a cloud it cannot serve is appended to ``host_path``."""
+        cfg, dev = self.cfg, self.device
+        cap, want, n_pool = k['cap'], k['want'], k['n_pool']
+        C_ = int(cfg.num_classes)
+        waiting = iter(members)
+
+        def admit_next():
+            """State of the next cloud, created as inference_begin creates it (None: no cloud is left)."""
+            for i in waiting:
+                data = self.preprocess(clouds[i], {'split': 'test'})
+                n = int(data['search_tree'].data.shape[0])
+                if n < 2:
+                    host_path.append(i)
+                    continue
+                rng = np.random.RandomState(seeds[i])
+                poss = rng.rand(n) * 1e-3
+                feat = None
+                if n_extra:
+                    feat = torch.from_numpy(np.ascontiguousarray(data['feat'], dtype=np.float32)).to(dev)
+                return dict(cloud=i, rng=rng, n=n, proj_inds=data['proj_inds'], have=0, cur=[], batches=0, spheres=0, retries=0,
+                            check=False, points=data['search_tree']._pts().contiguous(), possibility=torch.from_numpy(poss).to(dev),
+                            label=torch.from_numpy(np.ascontiguousarray(data['label'], dtype=np.int32)).to(dev), feat=feat,
+                            votes=torch.zeros((n, C_), dtype=torch.float16, device=dev))
+            return None
+
+        slots, buf = [], {}
+
+        def rebuild():
+            """Concatenated device arrays of the clouds in the slots: a newly admitted cloud brings its own tensors, the others are
+            views of the previous buffers (no sphere is pending at an admission: it happens at a batch boundary of ALL clouds)."""
+            for s_, st in enumerate(slots):
+                if st is not None and 'points' not in st:
+                    a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
+                    st.update(points=buf['points'][a:b], possibility=buf['possibility'][a:b], label=buf['label'][a:b],
+                              votes=buf['votes'][a:b], feat=None if buf['feat'] is None else buf['feat'][a:b])
+            live = [st for st in slots if st is not None]
+            splits = np.zeros(len(slots) + 1, np.int64)
+            np.cumsum([0 if st is None else st['n'] for st in slots], out=splits[1:])
+            new = dict(splits=splits, feat=None, splits_dev=torch.from_numpy(splits).to(dev))
+            for name in ('points', 'possibility', 'label', 'votes'):
+                new[name] = torch.cat([st[name] for st in live]).contiguous()
+            if n_extra:
+                new['feat'] = torch.cat([st['feat'] for st in live]).contiguous()
+            for st in live:
+                for name in ('points', 'possibility', 'label', 'votes', 'feat'):
+                    st.pop(name, None)
+            new['cand'] = torch.empty(int(splits[-1]), dtype=torch.int32, device=dev)
+            buf.clear()
+            buf.update(new)
+
+        def retire(s_):
+            st = slots[s_]
+            a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
+            probs = buf['votes'][a:b].cpu().numpy()
+            results[st['cloud']] = {'predict_labels': np.argmax(probs, 1)[st['proj_inds']], 'predict_scores': probs[st['proj_inds']]}
+            info[st['cloud']] = dict(num_batches=st['batches'], num_spheres=st['spheres'], retries=st['retries'],
+                                     possibility=buf['possibility'][a:b].cpu().numpy())
+            slots[s_] = None
+
+        while len(slots) < S:
+            st = admit_next()
+            if st is None:
+                break
+            slots.append(st)
+        if not slots:
+            return
+        rebuild()
+        nC = len(slots)
+        idx = torch.zeros(nC, dtype=torch.int32, device=dev)
+        mins = torch.zeros(nC, dtype=torch.float64, device=dev)
+        cnt = torch.zeros(nC, dtype=torch.int32, device=dev)
+        stage = dict(pinned=torch.empty(1 << 16, dtype=torch.int32).pin_memory(), dev=torch.empty(1 << 16, dtype=torch.int32, device=dev))
+        uploaded = torch.cuda.Event()
+        uploaded.record()
+        while True:
+            active = [s_ for s_, st in enumerate(slots) if st is not None]
+            if not active:
+                break
+            need = [s_ for s_ in active if slots[s_]['have'] < want]
+            if need:
+                # ---- one sub-round: the next sphere of every cloud whose batch is not complete ------------------------------------------
+                ops.possibility_argmin(buf['possibility'], buf['splits'], need, out=(idx, mins))
+                ops.sphere_select(buf['points'], buf['splits'], need, idx, float(cfg.in_radius), out=(buf['cand'], cnt))
+                host = torch.cat([mins, cnt.to(torch.float64)]).cpu().numpy()          # the ONE read-back of the sub-round
+                stats['read_backs'] += 1
+                stats['sub_rounds'] += 1
+                mins_h, cnt_h = host[:nC], host[nC:].astype(np.int64)
+                # the finished test runs at a cloud's batch boundary only, like inference_end
+                finished = [s_ for s_ in need if slots[s_]['check'] and mins_h[s_] > 0.5]
+                for s_ in need:
+                    slots[s_]['check'] = False
+                if finished:
+                    admitted = False
+                    for s_ in finished:
+                        retire(s_)
+                        st = admit_next()
+                        if st is not None:
+                            slots[s_] = st
+                            admitted = True
+                    if admitted:
+                        rebuild()                                 # (a batch boundary of every cloud: no sphere is pending)
+                    continue                                      # the sub-round starts again with the clouds now in the slots
+                offs = np.zeros(len(need) + 1, np.int64)
+                np.cumsum(cnt_h[need], out=offs[1:])
+                lonely = [s_ for s_ in need if cnt_h[s_] < 2]
+                if lonely:
+                    # fewer than 2 points: bump the centre and try again next sub-round, no draw consumed
+                    # (semseg_spatially_regular.py:78-96)
+                    sl = torch.as_tensor(lonely, dtype=torch.int64, device=dev)
+                    rows = idx[sl].to(torch.int64) + buf['splits_dev'][sl]
+                    buf['possibility'].index_add_(0, rows, torch.full((len(lonely),), 0.001, dtype=torch.float64, device=dev))
+                    for s_ in lonely:
+                        slots[s_]['retries'] += 1
+                go = [(a, s_) for a, s_ in enumerate(need) if cnt_h[s_] >= 2]
+                if not go:
+                    continue
+                t0 = time.perf_counter()
+                perms, keeps, m_a, zero = [], [], [], []
+                for a, s_ in go:
+                    st = slots[s_]
+                    n_s, budget = int(cnt_h[s_]), cap - st['have']
+                    perms.append(st['rng'].permutation(n_s).astype(np.int32))
+                    if n_s > budget:
+                        keeps.append(st['rng'].choice(n_s, size=budget, replace=False).astype(np.int32))
+                        m_a.append(budget)
+                    else:
+                        m_a.append(-1)
+                    self._draw_augmentation(min(n_s, budget), 3, st['rng'])     # is_test: the points stay, the draws are consumed
+                    zero.append(bool(st['rng'].rand() > cfg.augment_color))
+                host_ints = np.concatenate(perms + keeps)
+                stats['host_draw_seconds'] += time.perf_counter() - t0
+                # perms and cuts go up in ONE copy out of a pinned staging buffer whose previous upload has finished
+                uploaded.synchronize()
+                if host_ints.size > stage['pinned'].numel():
+                    size = 1 << int(host_ints.size - 1).bit_length()
+                    stage.update(pinned=torch.empty(size, dtype=torch.int32).pin_memory(), dev=torch.empty(size, dtype=torch.int32, device=dev))
+                stage['pinned'][:host_ints.size].copy_(torch.from_numpy(host_ints))
+                stage['dev'][:host_ints.size].copy_(stage['pinned'][:host_ints.size], non_blocking=True)
+                uploaded.record()
+                n_perm = int(sum(p_.size for p_ in perms))
+                pts, cols, sel, row, out_offs = ops.device_sphere_batch(
+                    buf['points'], buf['possibility'], buf['splits'], [s_ for _, s_ in go], idx, buf['cand'], [offs[a] for a, _ in go],
+                    [cnt_h[s_] for _, s_ in go], stage['dev'][:n_perm], stage['dev'][n_perm:host_ints.size] if keeps else None,
+                    m_a if keeps else None, zero, k['axes'], buf['feat'], k['bias'], k['scale'], k['linear'])
+                for j, (_, s_) in enumerate(go):
+                    st = slots[s_]
+                    a, b = int(out_offs[j]), int(out_offs[j + 1])
+                    st['cur'].append(dict(pts=pts[a:b], cols=cols[a:b], sel=sel[a:b], row=row[a:b], n=b - a))
+                    st['have'] += b - a
+                    st['spheres'] += 1
+                continue
+            # ---- every active cloud's batch is complete: one KPConvBatch over all their spheres, one forward -------------------------------
+            spheres, parts, rot = [], [], [[] for _ in range(n_pool)]
+            for s_ in active:
+                st = slots[s_]
+                for l in range(n_pool):              # the cloud's own grid orientations, in KPConvBatch's draw order
+                    rot[l].append(random_grid_rotations(len(st['cur']), st['rng']))
+                for o, sp in enumerate(st['cur']):
+                    spheres.append((st['cloud'], st['batches'], o))
+                    parts.append(sp)
+            pts_all = torch.cat([sp['pts'] for sp in parts]).contiguous()
+            cols_all = torch.cat([sp['cols'] for sp in parts])
+            row_all = torch.cat([sp['row'] for sp in parts])
+            batch = KPConvBatch(pts_all, [sp['n'] for sp in parts], cfg, features=self._device_input_features(cols_all, cfg.in_features_dim),
+                                rotations=[np.concatenate(r) for r in rot], device=dev)
+            batch.labels = buf['label'][row_all.long()].to(torch.int64)
+            batch.reproj_masks = [sp['sel'] for sp in parts]
+            batch.reproj_rows = [sp['row'] for sp in parts]
+            batch.pools_max = self._pools_of_own_batches(batch, [len(slots[s_]['cur']) for s_ in active])
+            logits = self(batch)
+            stats['forwards'] += 1
+            # votes: sphere ordinal by ordinal, so that a cloud's overlapping spheres are applied in sphere order; rows of different
+            # clouds are distinct and a sphere's points are distinct: the indices of each call are distinct
+            starts = np.concatenate([[0], np.cumsum([sp['n'] for sp in parts])])
+            for o in range(max(len(slots[s_]['cur']) for s_ in active)):
+                js = [j for j, sph in enumerate(spheres) if sph[2] == o]
+                ops.vote_update(buf['votes'], torch.cat([parts[j]['row'] for j in js]),
+                                torch.cat([logits[int(starts[j]):int(starts[j + 1])] for j in js]), self.test_smooth)
+            for s_ in active:
+                st = slots[s_]
+                st.update(cur=[], have=0, batches=st['batches'] + 1, check=True)
+            if on_batch is not None:
+                on_batch(spheres, batch, logits)
 
     def get_optimizer(self, cfg_pipeline):
         """kpconv.py:293-313: SGD with a separate learning rate for the deformable offsets' parameters."""
@@ -950,14 +1273,16 @@ KPConvBatch.to = _kpconv_batch_to
 KPConvBatch.pin_memory = lambda self: self
 
 
-def random_grid_rotations(B):
+def random_grid_rotations(B, rng=None):
     """The np.random draws of ``batch_grid_subsampling`` (kpconv.py:2059-2080) followed by the closed-form axis-angle
     rotation of ``create_3D_rotations`` (ml3d/datasets/utils/operations.py:21-40): same draw order and the same float64
-    operation order (temporaries t1 .. t24 as there), because the bit-exact batch golden depends on every rounding."""
-    theta = np.random.rand(B) * 2 * np.pi
-    phi = (np.random.rand(B) - 0.5) * np.pi
+    operation order (temporaries t1 .. t24 as there), because the bit-exact batch golden depends on every rounding.  ``rng``: a
+    ``np.random.RandomState`` to draw from instead of the global one."""
+    rng = np.random if rng is None else rng
+    theta = rng.rand(B) * 2 * np.pi
+    phi = (rng.rand(B) - 0.5) * np.pi
     u = np.vstack([np.cos(theta) * np.cos(phi), np.sin(theta) * np.cos(phi), np.sin(phi)]).T
-    alpha = np.random.rand(B) * 2 * np.pi
+    alpha = rng.rand(B) * 2 * np.pi
     t1 = np.cos(alpha)
     t2 = 1 - t1
     t3 = u[:, 0] * u[:, 0]
