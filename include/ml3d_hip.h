@@ -1190,6 +1190,62 @@ int ml3d_sparse_conv_bf16x3(const float* in, int64_t ldi, int64_t in_rows, int c
 int ml3d_scn_bn_relu(const float* in, int64_t ldi, int64_t m, int c, const float* scale, const float* shift, float* out,
                      int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* PointNet++ MSG backbone inference (added at ABI 13: new symbols only, no   */
+/*   signature changed) -- the reference's ml3d/torch/modules/pointnet.py and */
+/*   ml3d/torch/utils/pointnet/pointnet2_utils.py.  Kernel launches only.     */
+/* ------------------------------------------------------------------------- */
+/* ml3d_ball_query replaces open3d.ml.torch.ops.ball_query (pointnet2_utils.py:212) for ALL scales of a multi-scale-grouping  */
+/*   level in one scan.  points f32 [batch, n, 3], centres f32 [batch, m, 3]; radii_host f32 [scales], nsample_host int32      */
+/*   [scales] and out_host (one DEVICE pointer per scale: int32 [batch, m, nsample_s]) are HOST arrays, 1 <= scales <= 4.      */
+/*   CONTRACT (UNPINNED against the open3d wheel: the op lives in the wheel, which is not available to this project; the      */
+/*   semantics below are those of the Pointnet2.PyTorch kernel the wheel's op was taken from, stated operation by operation): */
+/*     dx = cx - x, dy = cy - y, dz = cz - z;  d2 = (dx * dx + dy * dy) + dz * dz   (float32, no fused multiply-add)          */
+/*     point j is a hit of scale s  iff  d2 < r_s * r_s            (the product formed in float32; d2 == r * r is NOT a hit)   */
+/*     out_s[b, i, :] = the first nsample_s hits in ASCENDING point index j (item-local); a centre with fewer hits fills the   */
+/*     remaining slots with its first hit; a centre without a hit gets all zeros.                                              */
+/*   One wave per centre, 64 points per step; the scan of a centre stops when every scale is full.  n < 2^31.                  */
+int ml3d_ball_query(const float* points, const float* centres, int64_t batch, int64_t n, int64_t m, int scales,
+                    const float* radii_host, const int32_t* nsample_host, int32_t* const* out_host, void* stream);
+
+/* ml3d_pn2_sa_mlp_max replaces QueryAndGroup's gather (pointnet2_utils.py:253-271), the three Conv2d(1x1) + BatchNorm2d +     */
+/*   ReLU of PointnetSAModuleMSG.mlps[s] and F.max_pool2d (pointnet.py:139-157) for ONE scale, without a                        */
+/*   [batch, c, m, nsample] tensor.  The first convolution is linear: W [p_j - c_i | f_j] = Wx (p_j - c_i) + y_j with           */
+/*   y = f Wf computed by the caller once per SOURCE point (ml3d_linear; NULL when the level has no features).  The position   */
+/*   part is evaluated on the exact difference (not as Wx p_j - Wx c_i, which cancels coordinates of tens of metres down to    */
+/*   a ball of decimetres).  Per centre i of item b, with j = idx[b, i, k] and d = points[b, j] - centres[b, i]:               */
+/*     h1[k] = relu((((w_x[0] dx + w_x[1] dy) + w_x[2] dz) + y[b * n + j]) + b1)                 k < nsample                     */
+/*     h2 = relu(h1 w2 + b2),  h3 = relu(h2 w3 + b3)      (f32 MFMA, the BatchNorm scale folded into the weights' columns)      */
+/*     out[b * m + i, :c3] = max over k of h3[k]          (rows of stride ldo: a column slice of the MSG output)               */
+/*   y rows [batch * n] of stride ldy (c1 columns: a slice of the product for all scales), points [batch, n, 3], centres       */
+/*   [batch, m, 3], idx int32                                                                                                   */
+/*   [batch, m, nsample] item-local (clamped into [0, n - 1]); w_x [3, c1], b1 [c1]; w2 [c1, c2p], b2 [c2p] and w3 [c2p, c3]   */
+/*   with c2p = c2 rounded up to a multiple of 32, the padding columns of w2 / b2 and rows of w3 ZERO; b3 [c3].                 */
+/*   Shapes (ml3d_pn2_sa_fused_supported): nsample 16 or 32, c1 even <= 128, c2p <= 128, c3 % 32 == 0 <= 128; everything else  */
+/*   returns ML3D_E_UNSUPPORTED and goes ml3d_pn2_group_rows -> ml3d_linear x 2 -> ml3d_segment_max_rows.                      */
+/*   An output row depends on its own nsample rows alone: a centre computed alone gives the same bits.                         */
+int ml3d_pn2_sa_fused_supported(int nsample, int c1, int c2, int c3);
+
+int ml3d_pn2_sa_mlp_max(const float* y, int64_t ldy, const float* points, const float* centres, const int32_t* idx,
+                        int64_t batch, int64_t n, int64_t m, int nsample, int c1, int c2, int c3, const float* w_x,
+                        const float* b1, const float* w2, const float* b2, const float* w3, const float* b3, float* out,
+                        int64_t ldo, void* stream);
+
+/* ml3d_pn2_group_rows: h1 of ml3d_pn2_sa_mlp_max alone, out rows [batch * m * nsample] of stride ldo (c1 columns), any shape. */
+int ml3d_pn2_group_rows(const float* y, int64_t ldy, const float* points, const float* centres, const int32_t* idx,
+                        int64_t batch, int64_t n, int64_t m, int nsample, int c1, const float* w_x, const float* b1,
+                        float* out, int64_t ldo, void* stream);
+
+/* ml3d_pn2_interpolate replaces PointnetFPModule.forward up to its MLP (pointnet.py:278-284: the weights and                   */
+/*   three_interpolate).  known rows [batch * m_known] of stride ldk (c columns); idx int32 [batch * n, 3] item-local (clamped  */
+/*   into [0, m_known - 1]) and dist2 f32 [batch * n, 3] SQUARED distances, as the exact 3-NN returns them.  float32:           */
+/*     w_t = 1 / (sqrtf(dist2_t) + 1e-8f),  norm = (w_0 + w_1) + w_2,  out[r, :c] = sum_t (w_t / norm) known[b * m_known + idx_t] */
+/*   out rows of stride ldo: the interpolated half of the concat buffer the FP MLP reads.  m_known < 3 is refused.              */
+/*   Exactly one of dist2 / weight is given: weight f32 [batch * n, 3] replaces w_t / norm by the caller's own weights          */
+/*   (three_interpolate, pointnet2_utils.py:162).                                                                               */
+int ml3d_pn2_interpolate(const float* known, int64_t ldk, int64_t batch, int64_t m_known, const int32_t* idx,
+                         const float* dist2, const float* weight, int64_t n, int c, float* out, int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

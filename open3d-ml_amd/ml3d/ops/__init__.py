@@ -25,3 +25,5 @@ from .pointtransformer import furthest_point_sampling, pt_attention, pt_transiti
 from .pvcnn import (pvcnn_voxel_coords, avg_voxelize, pack_conv3d_weights, conv3d_ndhwc, trilinear_devoxelize,   # noqa: F401
                     segment_max_rows, linear_rows_bf16x3)
 from .sparseconv import ScnPyramid, scn_build, pack_sparse_weights, sparse_conv, scn_bn_relu   # noqa: F401
+from .pointnet2 import (ball_query, three_nn, three_interpolate, pn2_interpolate, pn2_sa_mlp_max, pack_sa_weights,   # noqa: F401
+                        sa_fused)
