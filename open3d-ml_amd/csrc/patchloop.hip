@@ -93,12 +93,13 @@ pb_argmin_final(const double* __restrict__ part_v, const int* __restrict__ part_
     if (threadIdx.x == 0) { out_index[it.slot[a]] = idx; out_min[it.slot[a]] = v; }
 }
 
-// the centre of item a: the point its argmin picked (an index outside the cloud is clamped, never followed)
-__device__ __forceinline__ const float* pb_center(const float* __restrict__ pts, const PbItems& it, int a,
+// the centre of the cloud in `slot` (rows [start, start + len)): the point its argmin picked (an index outside the cloud is
+// clamped, never followed)
+__device__ __forceinline__ const float* pb_center(const float* __restrict__ pts, int start, int len, int slot,
                                                   const int32_t* __restrict__ center_index) {
-    int c = center_index[it.slot[a]];
-    c = c < 0 ? 0 : (c >= it.len[a] ? it.len[a] - 1 : c);
-    return pts + 3 * ((int64_t)it.start[a] + c);
+    int c = center_index[slot];
+    c = c < 0 ? 0 : (c >= len ? len - 1 : c);
+    return pts + 3 * ((int64_t)start + c);
 }
 
 // sort keys of the points of the active clouds: position cstart[a] + i <- (float64 reduced distance to the cloud's own centre, i)
@@ -108,7 +109,7 @@ pb_keys(const float* __restrict__ pts, PbItems it, const int32_t* __restrict__ c
     const int a = blockIdx.y;
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (i >= it.len[a]) return;
-    const float* c = pb_center(pts, it, a, center_index);
+    const float* c = pb_center(pts, it.start[a], it.len[a], it.slot[a], center_index);
     const float* p = pts + 3 * ((int64_t)it.start[a] + i);
     const double d2 = center_d2_f64(p[0], p[1], p[2], (double)c[0], (double)c[1], (double)c[2]);
     const int64_t pos = (int64_t)it.cstart[a] + i;
@@ -143,7 +144,7 @@ pb_gather(const float* __restrict__ pts, const uint32_t* __restrict__ sorted, Pb
         out_pts[3 * o] = x; out_pts[3 * o + 1] = y; out_pts[3 * o + 2] = z;
         out_sel[o] = i;
         out_row[o] = (int32_t)row;
-        d = patch_d2_f32(x, y, z, pb_center(pts, it, a, center_index));
+        d = patch_d2_f32(x, y, z, pb_center(pts, it.start[a], it.len[a], it.slot[a], center_index));
         d2[o] = d;
     }
     // max of non-negative floats == max of their bit patterns
@@ -199,7 +200,7 @@ ss_keys(const float* __restrict__ pts, PbItems it, const int32_t* __restrict__ c
     if ((int)blockIdx.x * 256 >= it.len[a]) return;           // (uniform over the workgroup)
     bool hit = false;
     if (i < it.len[a]) {
-        const float* c = pb_center(pts, it, a, center_index);
+        const float* c = pb_center(pts, it.start[a], it.len[a], it.slot[a], center_index);
         const float* p = pts + 3 * ((int64_t)it.start[a] + i);
         const float d2 = dist2_canon(c[0], c[1], c[2], p[0], p[1], p[2]);
         hit = d2 <= r2;
@@ -245,13 +246,6 @@ struct SbItems {
     int first;                 // ordinal of item 0 of this launch among the items of the call
 };
 
-__device__ __forceinline__ const float* sb_center(const float* __restrict__ pts, const SbItems& it, int a,
-                                                  const int32_t* __restrict__ center_index) {
-    int c = center_index[it.center[a]];
-    c = c < 0 ? 0 : (c >= it.len[a] ? it.len[a] - 1 : c);
-    return pts + 3 * ((int64_t)it.start[a] + c);
-}
-
 // picked = cand[perm]; distances to the centre and their maximum; sphere = p - centre (rows in the shuffle's order)
 __global__ void __launch_bounds__(256)
 sb_gather(const float* __restrict__ pts, SbItems it, const int32_t* __restrict__ center_index, const int32_t* __restrict__ cand,
@@ -268,7 +262,7 @@ sb_gather(const float* __restrict__ pts, SbItems it, const int32_t* __restrict__
         int i = cand[(int64_t)it.cand[a] + q];
         i = i < 0 ? 0 : (i >= it.len[a] ? it.len[a] - 1 : i);
         const int64_t row = (int64_t)it.start[a] + i;
-        const float* c = sb_center(pts, it, a, center_index);
+        const float* c = pb_center(pts, it.start[a], it.len[a], it.center[a], center_index);
         const float x = pts[3 * row], y = pts[3 * row + 1], z = pts[3 * row + 2];
         const int64_t o = (int64_t)it.in0[a] + j;
         d = patch_d2_f32(x, y, z, c);
@@ -387,6 +381,17 @@ static PbItems pb_items(const int64_t* splits, const int32_t* active, int64_t fi
     return it;
 }
 
+// the active clouds of a call in chunks of PB_ITEMS: launch(items of the chunk, their number, the longest of them)
+template <class F>
+static void pb_chunks(const int64_t* splits, const int32_t* active, int64_t n_active, F&& launch) {
+    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
+        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+        int longest;
+        const PbItems it = pb_items(splits, active, first, count, &longest);
+        launch(it, count, longest);
+    }
+}
+
 }  // namespace ml3d
 
 using namespace ml3d;
@@ -408,14 +413,11 @@ extern "C" int ml3d_possibility_argmin(const double* possibility, const int64_t*
     char* p = ws_align(workspace);
     double* part_v = (double*)p;  p += pb_al(sizeof(double) * tiles);
     int* part_i = (int*)p;
-    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
-        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
-        int longest;
-        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+    pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(pb_argmin_tiles, dim3((unsigned)((longest + PB_TILE - 1) / PB_TILE), (unsigned)count), dim3(256), 0, st,
                            possibility, it, part_v, part_i);
         hipLaunchKernelGGL(pb_argmin_final, dim3((unsigned)count), dim3(64), 0, st, part_v, part_i, it, out_index, out_min);
-    }
+    });
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
@@ -450,13 +452,10 @@ extern "C" int ml3d_patch_batch(const float* points, double* possibility, const 
     if (!sort_ws_carve(p, sort_ws_bytes(m), m, &sw)) return ML3D_E_WORKSPACE;
     zero_async(mx, pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active), st);      // (a fill kernel, not hipMemsetAsync: grid.h)
     const unsigned kblocks = (unsigned)((k + 255) / 256);
-    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
-        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
-        int longest;
-        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+    pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(pb_keys, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, points, it, center_index,
                            keys, vals, item_of);
-    }
+    });
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
     // all points of the active clouds by distance to their own cloud's centre, then ONE stable pass by cloud: every cloud's
     // points end up contiguous (in the order of the active list) and ascending in (distance, index)
@@ -469,13 +468,10 @@ extern "C" int ml3d_patch_batch(const float* points, double* possibility, const 
         if (sort_pairs_u64(keys, vals, m, bits, sw, st, true)) return ML3D_E_LAUNCH;
         if (sort_result_in_alt(m, bits)) sorted = sw.vals_alt;
     }
-    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
-        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
-        int longest;
-        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+    pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int) {
         hipLaunchKernelGGL(pb_gather, dim3(kblocks, (unsigned)count), dim3(256), 0, st, points, sorted, it, center_index, perm, k, out_pts,
                            out_sel, out_row, d2, mx);
-    }
+    });
     hipLaunchKernelGGL(pb_bump, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_row, d2, mx, k, possibility);
     if (dims_mask) hipLaunchKernelGGL(pb_mean_seq, dim3((unsigned)n_active), dim3(256), 0, st, out_pts, k, mean);
     hipLaunchKernelGGL(pb_apply, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_pts, k, dims_mask, mean, out_row, extra, n_extra,
@@ -507,25 +503,19 @@ extern "C" int ml3d_sphere_select(const float* points, const int64_t* cloud_row_
     if (!sort_ws_carve(p, sort_ws_bytes(m), m, &sw)) return ML3D_E_WORKSPACE;
     zero_async(cnt, pb_al(4 * (size_t)n_active), st);
     const float r2 = radius * radius;                                        // (ml3d_radius_fill's own bound)
-    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
-        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
-        int longest;
-        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+    pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(ss_keys, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, points, it, center_index,
                            r2, keys, vals, cnt);
-    }
+    });
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
     int bits = 32;
     while ((1ll << (bits - 32)) < n_active) ++bits;
     if (sort_pairs_u64(keys, vals, m, bits, sw, st, true)) return ML3D_E_LAUNCH;
     const uint32_t* sorted = sort_result_in_alt(m, bits) ? sw.vals_alt : vals;
-    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
-        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
-        int longest;
-        const PbItems it = pb_items(cloud_row_splits_host, active_host, first, count, &longest);
+    pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(ss_emit, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, sorted, it, cnt, out_index,
                            out_count);
-    }
+    });
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
@@ -566,19 +556,16 @@ extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const
     int32_t* row_of = (int32_t*)p;
     zero_async(mx, pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active), st);
     int64_t in0 = 0, keep0 = 0, out0 = 0;
-    for (int64_t first = 0; first < n_active; first += PB_ITEMS) {
-        const int count = n_active - first < PB_ITEMS ? (int)(n_active - first) : PB_ITEMS;
+    pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& cl, int count, int max_len) {
+        const int64_t first = cl.first;
         SbItems it;
-        int max_n = 0, max_m = 0, max_len = 0;
+        int max_n = 0, max_m = 0;
         for (int a = 0; a < PB_ITEMS; ++a) {
             const bool live = a < count;
-            const int64_t s = live ? active_host[first + a] : 0;
             const int64_t n = live ? n_host[first + a] : 0;
             const bool cut = live && keep && m_host[first + a] >= 0;
             const int64_t m = cut ? m_host[first + a] : n;
-            it.start[a] = live ? (int)cloud_row_splits_host[s] : 0;
-            it.len[a] = live ? (int)(cloud_row_splits_host[s + 1] - cloud_row_splits_host[s]) : 0;
-            it.center[a] = (int)s;
+            it.start[a] = cl.start[a]; it.len[a] = cl.len[a]; it.center[a] = cl.slot[a];
             it.cand[a] = live ? (int)cand_offset_host[first + a] : 0;
             it.n[a] = (int)n; it.in0[a] = (int)in0; it.keep0[a] = cut ? (int)keep0 : -1; it.out0[a] = (int)out0; it.m[a] = (int)m;
             it.zero[a] = live && zero_extra_host[first + a] ? 1 : 0;
@@ -586,9 +573,8 @@ extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const
             if (cut) keep0 += m;
             if (n > max_n) max_n = (int)n;
             if (m > max_m) max_m = (int)m;
-            if (it.len[a] > max_len) max_len = it.len[a];
         }
-        it.first = (int)first;
+        it.first = cl.first;
         const dim3 gn((unsigned)((max_n + 255) / 256), (unsigned)count), gm((unsigned)((max_m + 255) / 256), (unsigned)count);
         hipLaunchKernelGGL(sb_gather, gn, dim3(256), 0, st, points, it, center_index, cand, perm, sph, row_of, d2, mx);
         hipLaunchKernelGGL(sb_bump, gn, dim3(256), 0, st, it, row_of, d2, mx, possibility);
@@ -598,6 +584,6 @@ extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const
                                extra, it, n_extra, feat_bias, feat_scale);
         hipLaunchKernelGGL(sb_emit, gm, dim3(256), 0, st, it, sph, row_of, mean, keep, dims_mask, extra, n_extra, out_pts, out_columns,
                            out_sel, out_row);
-    }
+    });
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

@@ -107,6 +107,33 @@ def _host_splits(cloud_row_splits, active, what):
     return splits, act
 
 
+def _check_cloud_set(what, splits, act, min_len, points=None, possibility=None, center_index=None, extra=None, recenter_dims=()):
+    """What the multi-cloud entries take of a concatenated cloud set, checked against its host ``splits`` / ``act``: those given of
+    ``points`` float32 [N, 3], ``possibility`` float64 [N], ``center_index`` int32 [C] and the optional per-point ``extra`` float32
+    [N, c], and at least ``min_len`` points in every active cloud.  Returns (c, the bit mask of ``recenter_dims``)."""
+    n, n_clouds = int(splits[-1]), splits.size - 1
+    bad = bool(np.any(np.diff(splits)[act] < min_len))
+    if points is not None:
+        bad |= points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3)
+    if possibility is not None:
+        bad |= possibility.dtype != torch.float64 or not possibility.is_contiguous() or possibility.dim() != 1 or possibility.numel() != n
+    if center_index is not None:
+        bad |= center_index.dtype != torch.int32 or center_index.numel() != n_clouds or not center_index.is_contiguous()
+    if bad:
+        raise RuntimeError("%s: contiguous float32 [N, 3] points, float64 [N] possibilities and int32 [C] centre indices, "
+                           "N == cloud_row_splits[-1], at least %d points in every active cloud" % (what, min_len))
+    n_extra = 0
+    if extra is not None:
+        if extra.dtype != torch.float32 or not extra.is_contiguous() or extra.dim() != 2 or extra.shape[0] != n:
+            raise RuntimeError(what + ": extra must be a contiguous float32 [N, c] tensor")
+        _need_gpu(extra)
+        n_extra = int(extra.shape[1])
+    mask = 0
+    for d in recenter_dims:
+        mask |= 1 << int(d)
+    return n_extra, mask
+
+
 def possibility_argmin(possibility, cloud_row_splits, active=None, out=None):
     """Per cloud of a concatenated float64 ``possibility`` [N] (clouds delimited by the HOST ``cloud_row_splits`` [C + 1]): the
     FIRST index of its minimum (cloud-local, ``torch.argmin`` order) and the minimum -- (int32 [C], float64 [C]) device tensors,
@@ -117,9 +144,7 @@ def possibility_argmin(possibility, cloud_row_splits, active=None, out=None):
     splits, act = _host_splits(cloud_row_splits, active, "possibility_argmin")
     n_clouds = splits.size - 1
     dev = possibility.device
-    if possibility.dtype != torch.float64 or not possibility.is_contiguous() or possibility.dim() != 1 or \
-            possibility.numel() != int(splits[-1]) or np.any(np.diff(splits)[act] < 1):
-        raise RuntimeError("possibility_argmin: contiguous float64 [N] possibilities, N == cloud_row_splits[-1], no empty active cloud")
+    _check_cloud_set("possibility_argmin", splits, act, 1, possibility=possibility)
     if out is None:
         idx = torch.empty(n_clouds, dtype=torch.int32, device=dev)
         mins = torch.empty(n_clouds, dtype=torch.float64, device=dev)
@@ -152,19 +177,9 @@ def device_patch_batch(points, possibility, cloud_row_splits, active, center_ind
     splits, act = _host_splits(cloud_row_splits, active, "device_patch_batch")
     n_clouds, A, k = splits.size - 1, int(act.size), int(k)
     dev = points.device
-    n = int(splits[-1])
-    if points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3) or possibility.dtype != torch.float64 or \
-            not possibility.is_contiguous() or possibility.numel() != n or center_index.dtype != torch.int32 or \
-            center_index.numel() != n_clouds or not center_index.is_contiguous() or perm.dtype != torch.int32 or \
-            tuple(perm.shape) != (A, k) or not perm.is_contiguous() or k < 1 or np.any(np.diff(splits)[act] < k):
-        raise RuntimeError("device_patch_batch: float32 [N, 3] points, float64 [N] possibilities, N == cloud_row_splits[-1], int32 [C] "
-                           "centre indices, int32 [A, k] permutations, 1 <= k <= every active cloud's size")
-    n_extra = 0
-    if extra is not None:
-        if extra.dtype != torch.float32 or not extra.is_contiguous() or extra.dim() != 2 or extra.shape[0] != n:
-            raise RuntimeError("device_patch_batch: extra must be a contiguous float32 [N, c] tensor")
-        _need_gpu(extra)
-        n_extra = int(extra.shape[1])
+    if perm.dtype != torch.int32 or tuple(perm.shape) != (A, k) or not perm.is_contiguous() or k < 1:
+        raise RuntimeError("device_patch_batch: contiguous int32 [A, k] permutations, k >= 1")
+    n_extra, mask = _check_cloud_set("device_patch_batch", splits, act, k, points, possibility, center_index, extra, recenter_dims)
     if out is None:
         pts = torch.empty((A, k, 3), dtype=torch.float32, device=dev)
         feats = torch.empty((A, k, 3 + n_extra), dtype=torch.float32, device=dev)
@@ -176,9 +191,6 @@ def device_patch_batch(points, possibility, cloud_row_splits, active, center_ind
                 tuple(row.shape) != (A, k) or pts.dtype != torch.float32 or feats.dtype != torch.float32 or sel.dtype != torch.int32 or \
                 row.dtype != torch.int32 or not (pts.is_contiguous() and feats.is_contiguous() and sel.is_contiguous() and row.is_contiguous()):
             raise RuntimeError("device_patch_batch: out = (float32 [A, k, 3], float32 [A, k, 3 + c], int32 [A, k], int32 [A, k]), contiguous")
-    mask = 0
-    for d in recenter_dims:
-        mask |= 1 << int(d)
     m = int(np.diff(splits)[act].sum())
     wsb = lib.ml3d_patch_batch_workspace_bytes(m, A, k)
     ws = _ws(wsb, dev)
@@ -203,12 +215,10 @@ def sphere_select(points, cloud_row_splits, active, center_index, radius, out=No
     splits, act = _host_splits(cloud_row_splits, active, "sphere_select")
     n_clouds = splits.size - 1
     dev = points.device
-    n = int(splits[-1])
     m = int(np.diff(splits)[act].sum())
-    if points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3) or center_index.dtype != torch.int32 or \
-            center_index.numel() != n_clouds or not center_index.is_contiguous() or not float(radius) >= 0 or np.any(np.diff(splits)[act] < 1):
-        raise RuntimeError("sphere_select: float32 [N, 3] points, N == cloud_row_splits[-1], int32 [C] centre indices, radius >= 0, "
-                           "no empty active cloud")
+    if not float(radius) >= 0:
+        raise RuntimeError("sphere_select: radius >= 0")
+    _check_cloud_set("sphere_select", splits, act, 1, points, center_index=center_index)
     if out is None:
         idx = torch.empty(m, dtype=torch.int32, device=dev)
         cnt = torch.empty(n_clouds, dtype=torch.int32, device=dev)
@@ -244,17 +254,14 @@ def device_sphere_batch(points, possibility, cloud_row_splits, active, center_in
     splits, act = _host_splits(cloud_row_splits, active, "device_sphere_batch")
     n_clouds, A = splits.size - 1, int(act.size)
     dev = points.device
-    n = int(splits[-1])
     offs = np.ascontiguousarray(cand_offsets, dtype=np.int64).reshape(-1)
     n_a = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
-    lens = np.diff(splits)[act]
-    if points.dtype != torch.float32 or not points.is_contiguous() or tuple(points.shape) != (n, 3) or possibility.dtype != torch.float64 or \
-            not possibility.is_contiguous() or possibility.numel() != n or center_index.dtype != torch.int32 or \
-            center_index.numel() != n_clouds or not center_index.is_contiguous() or cand.dtype != torch.int32 or not cand.is_contiguous() or \
-            perm.dtype != torch.int32 or not perm.is_contiguous() or offs.size != A or n_a.size != A or np.any(n_a < 1) or \
-            np.any(n_a > lens) or np.any(offs < 0) or np.any(offs + n_a > cand.numel()) or perm.numel() != int(n_a.sum()):
-        raise RuntimeError("device_sphere_batch: float32 [N, 3] points, float64 [N] possibilities, N == cloud_row_splits[-1], int32 [C] "
-                           "centre indices, int32 candidates holding every item's list, 1 <= n_a <= the cloud's size, int32 [sum n_a] shuffles")
+    n_extra, mask = _check_cloud_set("device_sphere_batch", splits, act, 1, points, possibility, center_index, extra, recenter_dims)
+    if cand.dtype != torch.int32 or not cand.is_contiguous() or perm.dtype != torch.int32 or not perm.is_contiguous() or offs.size != A or \
+            n_a.size != A or np.any(n_a < 1) or np.any(n_a > np.diff(splits)[act]) or np.any(offs < 0) or \
+            np.any(offs + n_a > cand.numel()) or perm.numel() != int(n_a.sum()):
+        raise RuntimeError("device_sphere_batch: contiguous int32 candidates holding every item's list, 1 <= n_a <= the cloud's size, "
+                           "int32 [sum n_a] shuffles")
     m_a = None
     out_n = n_a.astype(np.int64)
     if keep is not None:
@@ -267,12 +274,6 @@ def device_sphere_batch(points, possibility, cloud_row_splits, active, center_in
     zero = np.zeros(A, np.int32) if zero_extra is None else np.ascontiguousarray(zero_extra).astype(np.int32).reshape(-1)
     if zero.size != A:
         raise RuntimeError("device_sphere_batch: one zero_extra flag per item")
-    n_extra = 0
-    if extra is not None:
-        if extra.dtype != torch.float32 or not extra.is_contiguous() or extra.dim() != 2 or extra.shape[0] != n:
-            raise RuntimeError("device_sphere_batch: extra must be a contiguous float32 [N, c] tensor")
-        _need_gpu(extra)
-        n_extra = int(extra.shape[1])
     out_offsets = np.zeros(A + 1, np.int64)
     np.cumsum(out_n, out=out_offsets[1:])
     M = int(out_offsets[-1])
@@ -280,9 +281,6 @@ def device_sphere_batch(points, possibility, cloud_row_splits, active, center_in
     cols = torch.empty((M, 3 + n_extra), dtype=torch.float32, device=dev)
     sel = torch.empty(M, dtype=torch.int32, device=dev)
     row = torch.empty(M, dtype=torch.int32, device=dev)
-    mask = 0
-    for d in recenter_dims:
-        mask |= 1 << int(d)
     wsb = lib.ml3d_sphere_batch_workspace_bytes(A, int(n_a.sum()))
     ws = _ws(wsb, dev)
     with torch.cuda.device(dev):

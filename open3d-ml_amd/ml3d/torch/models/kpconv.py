@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from ... import _abi
 from ... import ops
+from ._multicloud import CloudSlots, PinnedUpload, check_many_args
 
 
 class _Cfg(dict):
@@ -866,17 +867,9 @@ class KPFCNN(nn.Module):
         (``sampler_index='sklearn'``, a user-set ``trans_point_sampler``) or ``t_normalize.normalize_points`` is on (its whole-array
         ``mean()`` is a pairwise sum), and a cloud with fewer than 2 points after preprocessing."""
         import time
-        cfg, dev = self.cfg, self.device
-        _abi.require_gpu(dev, "KPFCNN.inference_many")
-        if self.training:
-            raise RuntimeError("KPFCNN.inference_many: call model.eval() first")
-        n_clouds, S = len(clouds), int(max_in_flight)
-        if S < 1 or S > 256:
-            raise ValueError("KPFCNN.inference_many: 1 <= max_in_flight <= 256")
-        if seeds is None:
-            seeds = [int(v) for v in np.random.randint(0, 2 ** 31 - 1, size=n_clouds)]
-        if len(seeds) != n_clouds:
-            raise ValueError("KPFCNN.inference_many: one seed per cloud")
+        cfg, n_clouds = self.cfg, len(clouds)
+        S, seeds = check_many_args("KPFCNN.inference_many", self, n_clouds, max_in_flight, seeds,
+                                   lambda n: [int(v) for v in np.random.randint(0, 2 ** 31 - 1, size=n)])
         norm = cfg.get('t_normalize', {})
         method = norm.get('method', None)
         axes = [int(a) for a in norm.get('recentering', [0, 1, 2])]
@@ -933,68 +926,37 @@ class KPFCNN(nn.Module):
                     feat = torch.from_numpy(np.ascontiguousarray(data['feat'], dtype=np.float32)).to(dev)
                 return dict(cloud=i, rng=rng, n=n, proj_inds=data['proj_inds'], have=0, cur=[], batches=0, spheres=0, retries=0,
                             check=False, points=data['search_tree']._pts().contiguous(), possibility=torch.from_numpy(poss).to(dev),
-                            label=torch.from_numpy(np.ascontiguousarray(data['label'], dtype=np.int32)).to(dev), feat=feat,
-                            votes=torch.zeros((n, C_), dtype=torch.float16, device=dev))
+                            label=torch.from_numpy(np.ascontiguousarray(data['label'], dtype=np.int32)).to(dev), feat=feat)
             return None
 
-        slots, buf = [], {}
+        def retired(st, result, possibility):
+            results[st['cloud']] = result
+            info[st['cloud']] = dict(num_batches=st['batches'], num_spheres=st['spheres'], retries=st['retries'], possibility=possibility)
 
-        def rebuild():
-            """Concatenated device arrays of the clouds in the slots: a newly admitted cloud brings its own tensors, the others are
-            views of the previous buffers (no sphere is pending at an admission: it happens at a batch boundary of ALL clouds)."""
-            for s_, st in enumerate(slots):
-                if st is not None and 'points' not in st:
-                    a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
-                    st.update(points=buf['points'][a:b], possibility=buf['possibility'][a:b], label=buf['label'][a:b],
-                              votes=buf['votes'][a:b], feat=None if buf['feat'] is None else buf['feat'][a:b])
-            live = [st for st in slots if st is not None]
-            splits = np.zeros(len(slots) + 1, np.int64)
-            np.cumsum([0 if st is None else st['n'] for st in slots], out=splits[1:])
-            new = dict(splits=splits, feat=None, splits_dev=torch.from_numpy(splits).to(dev))
-            for name in ('points', 'possibility', 'label', 'votes'):
-                new[name] = torch.cat([st[name] for st in live]).contiguous()
-            if n_extra:
-                new['feat'] = torch.cat([st['feat'] for st in live]).contiguous()
-            for st in live:
-                for name in ('points', 'possibility', 'label', 'votes', 'feat'):
-                    st.pop(name, None)
-            new['cand'] = torch.empty(int(splits[-1]), dtype=torch.int32, device=dev)
-            buf.clear()
-            buf.update(new)
+        def own_buffers():
+            """This loop's two additions to the table's rebuilt buffers: the splits on the device and the candidate lists' room."""
+            t.buf.update(splits_dev=torch.from_numpy(t.splits).to(dev), cand=torch.empty(int(t.splits[-1]), dtype=torch.int32, device=dev))
+            return t.buf
 
-        def retire(s_):
-            st = slots[s_]
-            a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
-            probs = buf['votes'][a:b].cpu().numpy()
-            results[st['cloud']] = {'predict_labels': np.argmax(probs, 1)[st['proj_inds']], 'predict_scores': probs[st['proj_inds']]}
-            info[st['cloud']] = dict(num_batches=st['batches'], num_spheres=st['spheres'], retries=st['retries'],
-                                     possibility=buf['possibility'][a:b].cpu().numpy())
-            slots[s_] = None
-
-        while len(slots) < S:
-            st = admit_next()
-            if st is None:
-                break
-            slots.append(st)
+        t = CloudSlots(S, admit_next, retired, dev, C_)
+        slots = t.slots
         if not slots:
             return
-        rebuild()
+        buf = own_buffers()
         nC = len(slots)
         idx = torch.zeros(nC, dtype=torch.int32, device=dev)
         mins = torch.zeros(nC, dtype=torch.float64, device=dev)
         cnt = torch.zeros(nC, dtype=torch.int32, device=dev)
-        stage = dict(pinned=torch.empty(1 << 16, dtype=torch.int32).pin_memory(), dev=torch.empty(1 << 16, dtype=torch.int32, device=dev))
-        uploaded = torch.cuda.Event()
-        uploaded.record()
+        upload = PinnedUpload(dev, 1 << 16)
         while True:
-            active = [s_ for s_, st in enumerate(slots) if st is not None]
+            active = t.active()
             if not active:
                 break
             need = [s_ for s_ in active if slots[s_]['have'] < want]
             if need:
                 # ---- one sub-round: the next sphere of every cloud whose batch is not complete ------------------------------------------
-                ops.possibility_argmin(buf['possibility'], buf['splits'], need, out=(idx, mins))
-                ops.sphere_select(buf['points'], buf['splits'], need, idx, float(cfg.in_radius), out=(buf['cand'], cnt))
+                ops.possibility_argmin(buf['possibility'], t.splits, need, out=(idx, mins))
+                ops.sphere_select(buf['points'], t.splits, need, idx, float(cfg.in_radius), out=(buf['cand'], cnt))
                 host = torch.cat([mins, cnt.to(torch.float64)]).cpu().numpy()          # the ONE read-back of the sub-round
                 stats['read_backs'] += 1
                 stats['sub_rounds'] += 1
@@ -1004,15 +966,8 @@ class KPFCNN(nn.Module):
                 for s_ in need:
                     slots[s_]['check'] = False
                 if finished:
-                    admitted = False
-                    for s_ in finished:
-                        retire(s_)
-                        st = admit_next()
-                        if st is not None:
-                            slots[s_] = st
-                            admitted = True
-                    if admitted:
-                        rebuild()                                 # (a batch boundary of every cloud: no sphere is pending)
+                    if t.replace_finished(finished):              # (a batch boundary of every cloud: no sphere is pending)
+                        buf = own_buffers()
                     continue                                      # the sub-round starts again with the clouds now in the slots
                 offs = np.zeros(len(need) + 1, np.int64)
                 np.cumsum(cnt_h[need], out=offs[1:])
@@ -1043,18 +998,11 @@ class KPFCNN(nn.Module):
                     zero.append(bool(st['rng'].rand() > cfg.augment_color))
                 host_ints = np.concatenate(perms + keeps)
                 stats['host_draw_seconds'] += time.perf_counter() - t0
-                # perms and cuts go up in ONE copy out of a pinned staging buffer whose previous upload has finished
-                uploaded.synchronize()
-                if host_ints.size > stage['pinned'].numel():
-                    size = 1 << int(host_ints.size - 1).bit_length()
-                    stage.update(pinned=torch.empty(size, dtype=torch.int32).pin_memory(), dev=torch.empty(size, dtype=torch.int32, device=dev))
-                stage['pinned'][:host_ints.size].copy_(torch.from_numpy(host_ints))
-                stage['dev'][:host_ints.size].copy_(stage['pinned'][:host_ints.size], non_blocking=True)
-                uploaded.record()
+                ints = upload.stage(host_ints)                    # perms and cuts go up in ONE copy
                 n_perm = int(sum(p_.size for p_ in perms))
                 pts, cols, sel, row, out_offs = ops.device_sphere_batch(
-                    buf['points'], buf['possibility'], buf['splits'], [s_ for _, s_ in go], idx, buf['cand'], [offs[a] for a, _ in go],
-                    [cnt_h[s_] for _, s_ in go], stage['dev'][:n_perm], stage['dev'][n_perm:host_ints.size] if keeps else None,
+                    buf['points'], buf['possibility'], t.splits, [s_ for _, s_ in go], idx, buf['cand'], [offs[a] for a, _ in go],
+                    [cnt_h[s_] for _, s_ in go], ints[:n_perm], ints[n_perm:] if keeps else None,
                     m_a if keeps else None, zero, k['axes'], buf['feat'], k['bias'], k['scale'], k['linear'])
                 for j, (_, s_) in enumerate(go):
                     st = slots[s_]

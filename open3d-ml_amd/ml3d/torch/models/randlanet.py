@@ -18,6 +18,7 @@ from ... import _abi
 from ... import ops
 from . import _randla_pack
 from ._datapath import GpuSearchTree, preprocess_segmentation   # noqa: F401
+from ._multicloud import CloudSlots, PinnedUpload, check_many_args
 
 
 class SharedMLP(nn.Module):
@@ -557,22 +558,24 @@ class RandLANet(nn.Module):
                                out=([v['nbr%d' % l] for l in range(cfg.num_layers)], [v['itp%d' % l] for l in range(cfg.num_layers)]))
         torch.index_select(st['label'], 0, v['sel'].long(), out=v['labels'])      # (int64 labels cast once per cloud)
 
-    def _inputs_from_arena(self, arena, lay):
+    def _forward_inputs(self, pts, nbr, itp, feats, sel, labels):
+        """The forward's input dict of one device patch (``pts`` [k, 3]) or of a batch of them ([A, k, 3]); ``nbr`` / ``itp``: the
+        pyramid's per-level index lists with the same leading dimensions."""
         cfg = self.cfg
-        k = int(cfg.num_points)
-        v = self._arena_views(arena, lay)
-        inputs, coords, n = dict(), [], k
+        k = int(pts.shape[-2])
+        coords, n = [], k
         for i in range(cfg.num_layers):
-            coords.append(v['pts'][:n])
+            coords.append(pts[..., :n, :])
             n = n // cfg.sub_sampling_ratio[i]
-        nbr = [v['nbr%d' % l] for l in range(cfg.num_layers)]
-        inputs['coords'] = coords
-        inputs['neighbor_indices'] = [t[0] for t in nbr]
-        inputs['sub_idx'] = [_mark_prefix(nbr[i][0, :k // int(np.prod(cfg.sub_sampling_ratio[:i + 1]))]) for i in range(cfg.num_layers)]
-        inputs['interp_idx'] = [v['itp%d' % l][0] for l in range(cfg.num_layers)]
-        inputs['features'] = v['feats']
-        inputs['point_inds'] = v['sel']
-        inputs['labels'] = v['labels']
+        return dict(coords=coords, neighbor_indices=nbr,
+                    sub_idx=[_mark_prefix(nbr[i][..., :k // int(np.prod(cfg.sub_sampling_ratio[:i + 1])), :]) for i in range(cfg.num_layers)],
+                    interp_idx=itp, features=feats, point_inds=sel, labels=labels)
+
+    def _inputs_from_arena(self, arena, lay):
+        v = self._arena_views(arena, lay)
+        levels = range(self.cfg.num_layers)
+        inputs = self._forward_inputs(v['pts'], [v['nbr%d' % l][0] for l in levels], [v['itp%d' % l][0] for l in levels], v['feats'],
+                                      v['sel'], v['labels'])
         # the forward recognises a patch of this loop by its arena (``_stack`` of this package's batcher carries the mark through a
         # batch of one): one copy into the forward graph's static inputs instead of ~30 launches
         inputs['features']._ml3d_arena = (arena, id(lay))
@@ -587,19 +590,13 @@ class RandLANet(nn.Module):
         if st.get('layout') is None:
             st['layout'] = self._arena_layout()
         lay, nbytes = st['layout']
-        perm_host = torch.from_numpy(self.rng.permutation(k).astype(np.int32))
+        perm_host = self.rng.permutation(k).astype(np.int32)
         g = self._patch_graph(lay, nbytes) if getattr(self, 'use_graphs', True) else None
         if g is None:
             arena = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            self._patch_into(self._arena_views(arena, lay), perm_host.to(dev))
+            self._patch_into(self._arena_views(arena, lay), torch.from_numpy(perm_host).to(dev))
             return self._inputs_from_arena(arena, lay)
-        # the shuffle goes through ONE pinned staging buffer: its previous upload has long finished, but the event makes that a
-        # fact before the buffer is overwritten (an asynchronous copy out of pageable memory that is freed right after the call
-        # faulted on the MI355X: "write access to a read-only page")
-        g['uploaded'].synchronize()
-        g['perm_pinned'].copy_(perm_host)
-        g['perm'].copy_(g['perm_pinned'], non_blocking=True)
-        g['uploaded'].record()
+        g['upload'].stage(perm_host)              # into g['perm'], the static tensor the captured graph reads
         g['graph'].replay()
         return self._inputs_from_arena(g['arena'].clone(), lay)
 
@@ -629,10 +626,8 @@ class RandLANet(nn.Module):
                     self._patch_into(v, perm)
                 torch.cuda.current_stream().synchronize()
                 st['possibility'].copy_(keep)
-                uploaded = torch.cuda.Event()
-                uploaded.record()
-            g = st['graph'] = dict(graph=graph, arena=arena, perm=perm, uploaded=uploaded,
-                                   perm_pinned=torch.empty(perm.numel(), dtype=torch.int32).pin_memory())
+                upload = PinnedUpload(dev, perm.numel(), into=perm)
+            g = st['graph'] = dict(graph=graph, arena=arena, perm=perm, upload=upload)
         except Exception as e:                                  # capture is an optimisation: the eager loop is always there
             st['graph_failed'] = "%s: %s" % (type(e).__name__, e)
             try:
@@ -704,17 +699,9 @@ class RandLANet(nn.Module):
         know) runs through the single-cloud loop on its own afterwards, with its generator.
         ``self.inference_many_info[i]`` keeps, per cloud, ``num_patches`` and its final ``possibility`` (numpy float64)."""
         cfg, dev = self.cfg, self.device
-        _abi.require_gpu(dev, "RandLANet.inference_many")
-        if self.training:
-            raise RuntimeError("RandLANet.inference_many: call model.eval() first")
         n_clouds = len(clouds)
-        S = int(max_in_flight)
-        if S < 1 or S > 256:
-            raise ValueError("RandLANet.inference_many: 1 <= max_in_flight <= 256")
-        if seeds is None:
-            seeds = [int(s) for s in self.rng.integers(0, 2 ** 63 - 1, size=n_clouds)]
-        if len(seeds) != n_clouds:
-            raise ValueError("RandLANet.inference_many: one seed per cloud")
+        S, seeds = check_many_args("RandLANet.inference_many", self, n_clouds, max_in_flight, seeds,
+                                   lambda n: [int(s) for s in self.rng.integers(0, 2 ** 63 - 1, size=n)])
         self.test_smooth = 0.95
         k, C_ = int(cfg.num_points), int(cfg.num_classes)
         results = [None] * n_clouds
@@ -732,102 +719,44 @@ class RandLANet(nn.Module):
                 if st is None:
                     host_path.append(i)
                     continue
-                st.update(cloud=i, rng=rng, proj_inds=data['proj_inds'], n=int(n), patches=0,
-                          votes=torch.zeros((n, C_), dtype=torch.float16, device=dev))
+                st.update(cloud=i, rng=rng, proj_inds=data['proj_inds'], n=int(n), patches=0)
                 return st
             return None
 
-        slots = []                 # per slot: the cloud's state (None once retired); the buffers below are their concatenation
-        buf = {}
+        def retired(st, result, possibility):
+            results[st['cloud']] = result
+            info[st['cloud']] = dict(num_patches=st['patches'], possibility=possibility)
 
-        def rebuild():
-            """Concatenated device arrays of the clouds in the slots (one copy per array): a newly admitted cloud brings its own
-            tensors, the others are views of the previous buffers.  A retired slot keeps no rows."""
-            for s_, st in enumerate(slots):
-                if st is not None and 'points' not in st:        # lives in the old buffers
-                    a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
-                    st.update(points=buf['points'][a:b], possibility=buf['possibility'][a:b], label=buf['label'][a:b],
-                              votes=buf['votes'][a:b], feat=None if buf['feat'] is None else buf['feat'][a:b])
-            live = [st for st in slots if st is not None]
-            splits = np.zeros(len(slots) + 1, np.int64)
-            np.cumsum([0 if st is None else st['n'] for st in slots], out=splits[1:])
-            new = dict(splits=splits, feat=None)
-            for name in ('points', 'possibility', 'label', 'votes'):
-                new[name] = torch.cat([st[name] for st in live]).contiguous()
-            if live[0]['feat'] is not None:
-                new['feat'] = torch.cat([st['feat'] for st in live]).contiguous()
-            for st in live:
-                for name in ('points', 'possibility', 'label', 'votes', 'feat'):
-                    st.pop(name, None)
-            buf.clear()
-            buf.update(new)
-
-        def retire(s_):
-            st = slots[s_]
-            a, b = int(buf['splits'][s_]), int(buf['splits'][s_ + 1])
-            probs = buf['votes'][a:b].cpu().numpy()
-            results[st['cloud']] = {'predict_labels': np.argmax(probs, 1)[st['proj_inds']], 'predict_scores': probs[st['proj_inds']]}
-            info[st['cloud']] = dict(num_patches=st['patches'], possibility=buf['possibility'][a:b].cpu().numpy())
-            slots[s_] = None
-
-        while len(slots) < S:
-            st = admit_next()
-            if st is None:
-                break
-            slots.append(st)
+        t = CloudSlots(S, admit_next, retired, dev, C_)
+        slots = t.slots
         if slots:
-            rebuild()
             idx = torch.zeros(len(slots), dtype=torch.int32, device=dev)
             mins = torch.zeros(len(slots), dtype=torch.float64, device=dev)
-            perm_pinned = torch.empty((len(slots), k), dtype=torch.int32).pin_memory()
-            perm_dev = torch.empty((len(slots), k), dtype=torch.int32, device=dev)
-            uploaded = torch.cuda.Event()
-            uploaded.record()
-        active = [s_ for s_, st in enumerate(slots) if st is not None]
+            upload = PinnedUpload(dev, len(slots) * k)
+        active = t.active()
         while active:
-            ops.possibility_argmin(buf['possibility'], buf['splits'], active, out=(idx, mins))
+            ops.possibility_argmin(t.buf['possibility'], t.splits, active, out=(idx, mins))
             mins_host = mins.cpu().numpy()                           # the ONE read-back of the round
             finished = [s_ for s_ in active if mins_host[s_] > 0.5]
             if finished:
-                admitted = False
-                for s_ in finished:
-                    retire(s_)
-                    st = admit_next()
-                    if st is not None:
-                        slots[s_] = st
-                        admitted = True
-                active = [s_ for s_, st in enumerate(slots) if st is not None]
+                rebuilt = t.replace_finished(finished)
+                active = t.active()
                 if not active:
                     break
-                if admitted:
-                    rebuild()                                        # one device copy per admission, not per round
+                if rebuilt:
                     # (a fresh cloud's possibilities are < 1e-3: nothing to read back, only its centre is needed)
-                    ops.possibility_argmin(buf['possibility'], buf['splits'], active, out=(idx, mins))
-            A = len(active)
-            # the A shuffles go up in ONE copy out of a pinned staging buffer whose previous upload has finished (see the note in
-            # _transform_device about asynchronous copies out of pageable memory)
-            uploaded.synchronize()
+                    ops.possibility_argmin(t.buf['possibility'], t.splits, active, out=(idx, mins))
+            A, buf = len(active), t.buf
+            perms = np.empty((A, k), np.int32)
             for a, s_ in enumerate(active):
                 slots[s_]['patches'] += 1
-                perm_pinned[a].copy_(torch.from_numpy(slots[s_]['rng'].permutation(k).astype(np.int32)))
-            perm_dev[:A].copy_(perm_pinned[:A], non_blocking=True)
-            uploaded.record()
+                perms[a] = slots[s_]['rng'].permutation(k)
             first = slots[active[0]]
-            pts, feats, sel, row = ops.device_patch_batch(buf['points'], buf['possibility'], buf['splits'], active, idx, perm_dev[:A], k,
+            pts, feats, sel, row = ops.device_patch_batch(buf['points'], buf['possibility'], t.splits, active, idx,
+                                                          upload.stage(perms).view(A, k), k,      # the A shuffles: ONE copy per round
                                                           first['dims'], buf['feat'], first['bias'], first['scale'])
             nbr, itp = ops.randla_knn_pyramid(pts, cfg.sub_sampling_ratio, cfg.num_neighbors)
-            labels = buf['label'][row.long()]
-            inputs, coords, n = dict(), [], k
-            for i in range(cfg.num_layers):
-                coords.append(pts[:, :n])
-                n = n // cfg.sub_sampling_ratio[i]
-            inputs['coords'] = coords
-            inputs['neighbor_indices'] = nbr
-            inputs['sub_idx'] = [_mark_prefix(nbr[i][:, :k // int(np.prod(cfg.sub_sampling_ratio[:i + 1]))]) for i in range(cfg.num_layers)]
-            inputs['interp_idx'] = itp
-            inputs['features'] = feats
-            inputs['point_inds'] = sel
-            inputs['labels'] = labels
+            inputs = self._forward_inputs(pts, nbr, itp, feats, sel, buf['label'][row.long()])
             logits = self(inputs)
             # rows of different clouds are distinct and a cloud's k nearest are distinct: the indices of this ONE call are distinct
             ops.vote_update(buf['votes'], row.reshape(-1), logits.reshape(-1, C_), self.test_smooth)
