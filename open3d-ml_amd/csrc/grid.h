@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "workspace.h"
+
 namespace ml3d {
 
 constexpr int GRID_CAP = 8;      // dense cell table: at most GRID_CAP * n + 64 cells per segment
@@ -65,10 +67,11 @@ struct GridWs {
     int batch;
 };
 
-constexpr int GRID_SORTED_SLACK = 4;     // float4 entries kept readable behind GridWs::sorted (see grid_ws_bytes)
+constexpr int GRID_SORTED_SLACK = 4;     // float4 entries kept readable behind GridWs::sorted (see grid_ws)
+// THE layout of a grid's workspace (workspace.h): ws_bytes_of(grid_ws, ...) measures it, ws_nest(L, grid_ws, ...) puts it into
+// another op's workspace
+GridWs grid_ws(WsLayout& L, int64_t n_total, int64_t batch);
 size_t grid_ws_bytes(int64_t n_total, int64_t batch);
-// carve `ws` (must hold grid_ws_bytes) — returns false if too small
-bool grid_ws_carve(void* ws, size_t bytes, int64_t n_total, int64_t batch, GridWs* out);
 // enqueue the build; `points` row = 3 floats.  target_occ <= 0 -> default.
 int grid_build(const float* points, Segs segs, const GridWs& ws, float target_occ, hipStream_t stream);
 // Build the grid of a SUBSET of the points of `parent` (same batch items, e.g. the RandLA prefix
@@ -87,10 +90,6 @@ int scan_inclusive_i32(int* a, int64_t n, int* block_sums, hipStream_t stream);
 // zero `bytes` (a multiple of 4) at a 16-byte aligned device address with a fill KERNEL: what every op that may be captured into a
 // HIP graph uses instead of hipMemsetAsync (ROCm 7.2: a graph's memset node did not clear its target on later replays, grid.hip)
 void zero_async(void* ptr, size_t bytes, hipStream_t stream);
-
-// a caller's workspace from its first 256-byte boundary on (null stays null), and what is left of `bytes` whatever the alignment cost
-static inline char* ws_align(void* ws) { return (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255); }
-static inline size_t ws_avail(const void* ws, size_t bytes) { return ws && bytes > 256 ? bytes - 256 : 0; }
 
 // order-preserving float <-> uint so atomicMin/atomicMax work on floats
 __device__ __forceinline__ unsigned f2ord(float f) {

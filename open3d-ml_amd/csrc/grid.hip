@@ -11,8 +11,6 @@
 
 namespace ml3d {
 
-static inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static void grid_sizes(int64_t n_total, int64_t batch, int64_t* total_cells, int64_t* bitmap_words,
                        int64_t* n_blocks) {
     *total_cells = (int64_t)GRID_CAP * n_total + (int64_t)GRID_SLACK * batch;
@@ -20,39 +18,27 @@ static void grid_sizes(int64_t n_total, int64_t batch, int64_t* total_cells, int
     *n_blocks = (*total_cells + 2 + 1023) / 1024 + 1;
 }
 
-size_t grid_ws_bytes(int64_t n_total, int64_t batch) {
+// (bitmap and cells stay neighbours: grid_build zeroes both with one fill)
+GridWs grid_ws(WsLayout& L, int64_t n_total, int64_t batch) {
     int64_t tc, bw, nb;
     grid_sizes(n_total, batch, &tc, &bw, &nb);
-    size_t b = 0;
-    b += align_up(sizeof(GridSeg) * (size_t)batch);
-    b += align_up(sizeof(unsigned) * 6 * (size_t)batch);
-    b += align_up(sizeof(unsigned) * GRID_LEVELS * (size_t)batch);
-    b += align_up(sizeof(unsigned) * GRID_LEVELS * (size_t)bw);
-    b += align_up(sizeof(int) * (size_t)(tc + 2));
-    b += align_up(sizeof(int) * (size_t)nb);
+    GridWs o;
+    o.segs = L.take<GridSeg>((size_t)batch);
+    o.bbox = L.take<unsigned>(6 * (size_t)batch);
+    o.occ = L.take<unsigned>(GRID_LEVELS * (size_t)batch);
+    o.bitmap = L.take<unsigned>(GRID_LEVELS * (size_t)bw);
+    o.cells = L.take<int>((size_t)(tc + 2));
+    o.block_sums = L.take<int>((size_t)nb);
     // (+ GRID_SORTED_SLACK entries behind the cell-sorted array: the k-NN scan reads a few entries past a run's end, knn.hip scan_run)
-    b += align_up(sizeof(float4) * (size_t)((n_total > 0 ? n_total : 1) + GRID_SORTED_SLACK));
-    return b + 256;
+    o.sorted = L.take<float4>((size_t)((n_total > 0 ? n_total : 1) + GRID_SORTED_SLACK));
+    o.total_cells = tc;
+    o.bitmap_words = bw;
+    o.n_total = n_total;
+    o.batch = (int)batch;
+    return o;
 }
 
-bool grid_ws_carve(void* ws, size_t bytes, int64_t n_total, int64_t batch, GridWs* out) {
-    if (bytes < grid_ws_bytes(n_total, batch)) return false;
-    int64_t tc, bw, nb;
-    grid_sizes(n_total, batch, &tc, &bw, &nb);
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    out->segs = (GridSeg*)p;      p += align_up(sizeof(GridSeg) * (size_t)batch);
-    out->bbox = (unsigned*)p;     p += align_up(sizeof(unsigned) * 6 * (size_t)batch);
-    out->occ = (unsigned*)p;      p += align_up(sizeof(unsigned) * GRID_LEVELS * (size_t)batch);
-    out->bitmap = (unsigned*)p;   p += align_up(sizeof(unsigned) * GRID_LEVELS * (size_t)bw);
-    out->cells = (int*)p;         p += align_up(sizeof(int) * (size_t)(tc + 2));
-    out->block_sums = (int*)p;    p += align_up(sizeof(int) * (size_t)nb);
-    out->sorted = (float4*)p;
-    out->total_cells = tc;
-    out->bitmap_words = bw;
-    out->n_total = n_total;
-    out->batch = (int)batch;
-    return true;
-}
+size_t grid_ws_bytes(int64_t n_total, int64_t batch) { return ws_bytes_of(grid_ws, n_total, batch); }
 
 // ---- K1: bounding box per segment -------------------------------------------------------------
 __global__ void grid_bbox_init(unsigned* bbox, unsigned* occ, int batch) {
@@ -558,7 +544,7 @@ __global__ void grid_scatter(const float* __restrict__ pts, Segs S, int64_t n_to
 // Zero fill of the cell tables as a KERNEL, not hipMemsetAsync: on ROCm 7.2 a memset node of a captured HIP graph (the model-class
 // patch loop replays this build as a graph) did not reliably clear the table on the second and later replays -- the stale
 // histogram sent grid_scatter out of bounds ("write access to a read-only page", gpurun r5g).  16-byte stores, tail by words;
-// both pointers in the workspace are 256-byte aligned (grid_ws_carve) and the lengths multiples of 4.
+// both pointers in the workspace are 256-byte aligned (grid_ws) and the lengths multiples of 4.
 __global__ void __launch_bounds__(256) grid_zero(uint4* __restrict__ p, size_t n16, uint32_t* __restrict__ tail, int ntail) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t step = (size_t)gridDim.x * blockDim.x;
@@ -619,7 +605,7 @@ int grid_build(const float* points, Segs S, const GridWs& ws, float target_occ, 
     if (B <= 0) return 0;
     if (target_occ <= 0.f) target_occ = 4.0f;
     int sb = (B + 63) / 64;
-    // (bitmap and cell table are neighbours in the workspace, grid_ws_carve: one fill instead of two)
+    // (bitmap and cell table are neighbours in the workspace, grid_ws: one fill instead of two)
     zero_async(ws.bitmap, (size_t)((char*)(ws.cells + ws.total_cells + 2) - (char*)ws.bitmap), stream);
     hipLaunchKernelGGL(grid_bbox_init, dim3(sb), dim3(64), 0, stream, ws.bbox, ws.occ, B);
     ML3D_LAUNCH_CHECK();

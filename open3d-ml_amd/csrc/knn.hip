@@ -403,17 +403,13 @@ static int knn_block() { return 64; }
 //  waves on 5120 slots -- measured: 0.363 -> 0.342 ms at batch 1, i.e. a launch that small is not bound by what shares a wave
 //  (the suspect: its slowest single query, an outlier walking hundreds of near-empty rows, two dependent loads each).  Removed.)
 // hand-off scratch behind the grids of a pyramid workspace: room for 5/8 of the queries (measured: ~44 % go past the first shell)
-static size_t handoff_bytes(int64_t total_queries) {
+static Handoff handoff_ws(WsLayout& L, int64_t total_queries) {
     const size_t cap = (size_t)(total_queries * 5 / 8 + 64);
-    return 256 + ((cap * 4 + 255) & ~(size_t)255) + 17 * cap * 8 + 256;
-}
-static Handoff handoff_carve(char* p, int64_t total_queries) {
     Handoff H;
-    const size_t cap = (size_t)(total_queries * 5 / 8 + 64);
-    p = (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-    H.count = (unsigned*)p;  p += 256;
-    H.who = (uint32_t*)p;    p += (cap * 4 + 255) & ~(size_t)255;
-    H.keys = (double*)p;
+    H.count = L.take<unsigned>(64);
+    H.who = L.take<uint32_t>(cap);
+    H.keys = L.take<double>(0);        // [17][cap], the tail
+    L.pad(17 * cap * 8);
     H.cap = (unsigned)cap;
     return H;
 }
@@ -510,7 +506,7 @@ extern "C" int ml3d_knn_search(const float* points, const int64_t* points_row_sp
     if (n_queries == 0) return 0;
     if (!out_index || (n_points > 0 && !points) || !queries) return ML3D_E_INVALID;
     GridWs ws;
-    if (!grid_ws_carve(workspace, workspace_bytes, n_points, batch, &ws)) return ML3D_E_WORKSPACE;
+    if (!ws_carve(workspace, workspace_bytes, &ws, grid_ws, n_points, batch)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Segs ps = {points_row_splits, 0, 0, (int)batch};
     Segs qs = {queries_row_splits, 0, 0, (int)batch};
@@ -536,15 +532,24 @@ static int pyramid_sizes(int64_t n0, int num_layers, const int32_t* ratios, int6
     return 0;
 }
 
+// a pyramid workspace: the grid of every level, 256 bytes of slack behind each, then the hand-off scratch.  n = pyramid_sizes
+static Handoff pyramid_ws(WsLayout& L, int64_t batch, int num_layers, const int64_t* n, GridWs* ws) {
+    int64_t total = 0;
+    for (int l = 0; l < num_layers; ++l) {
+        ws[l] = ws_nest(L, grid_ws, n[l] * batch, batch);
+        L.pad(256);
+        total += n[l] * batch;
+    }
+    return handoff_ws(L, total);
+}
+
 extern "C" size_t ml3d_randla_pyramid_workspace_bytes(int64_t batch, int64_t n0, int num_layers,
                                                       const int32_t* ratios_host) {
     if (num_layers <= 0 || num_layers > KNN_MAX_JOBS || !ratios_host) return 0;
     int64_t n[17];
     if (pyramid_sizes(n0, num_layers, ratios_host, n)) return 0;
-    size_t b = 0;
-    int64_t total = 0;
-    for (int l = 0; l < num_layers; ++l) { b += grid_ws_bytes(n[l] * batch, batch) + 256; total += n[l] * batch; }
-    return b + handoff_bytes(total);
+    GridWs ws[17];
+    return ws_bytes_of(pyramid_ws, batch, num_layers, n, ws);
 }
 
 extern "C" int ml3d_randla_knn_pyramid(const float* points, int64_t batch, int64_t n0, int num_layers,
@@ -578,16 +583,10 @@ extern "C" int ml3d_randla_knn_pyramid_ordered(const float* points, int64_t batc
     int64_t n[17];
     if (pyramid_sizes(n0, num_layers, ratios_host, n)) return ML3D_E_INVALID;
     if (n0 * batch > 0x7fffffffll / GRID_CAP - 4096) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_randla_pyramid_workspace_bytes(batch, n0, num_layers, ratios_host))
-        return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     GridWs ws[17];
-    char* p = (char*)workspace;
-    for (int l = 0; l < num_layers; ++l) {
-        size_t bytes = grid_ws_bytes(n[l] * batch, batch) + 256;
-        if (!grid_ws_carve(p, bytes, n[l] * batch, batch, &ws[l])) return ML3D_E_WORKSPACE;
-        p += bytes;
-    }
+    Handoff hand;
+    if (!ws_carve(workspace, workspace_bytes, &hand, pyramid_ws, batch, num_layers, n, ws)) return ML3D_E_WORKSPACE;
     float occ = tuning_occ();
     // grids of the searched levels: level l = prefix [:n_l] of each cloud (randlanet.py:222)
     for (int l = 0; l < num_layers; ++l) {
@@ -625,9 +624,6 @@ extern "C" int ml3d_randla_knn_pyramid_ordered(const float* points, int64_t batc
         a.out_sub = interp_idx_host[l];
         a.n_sub = (int)n[l + 1];          // 0: every interpolation index comes out -1 (no coarser level)
     }
-    int64_t total_q = 0;
-    for (int l = 0; l < num_layers; ++l) total_q += n[l] * batch;
-    const Handoff hand = handoff_carve(p, total_q);
     tb(0);
     int rc = launch_query_multi<true>(Jk, k, 1, st, &hand);
     te(0);
@@ -774,11 +770,19 @@ extern "C" int ml3d_argmax_labels(const float* scores, int64_t n, int num_classe
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
-extern "C" size_t ml3d_nearest_to_center_workspace_bytes(int64_t n_points) {
-    if (n_points < 0) return 0;
+struct CenterWs { u64* keys; uint32_t* vals; SortWs sort; };
+static CenterWs center_ws(WsLayout& L, int64_t n_points) {
     const int64_t m = n_points > 0 ? n_points : 1;
-    return ((sizeof(u64) * (size_t)m + 255) & ~(size_t)255) + ((sizeof(uint32_t) * (size_t)m + 255) & ~(size_t)255) +
-           sort_ws_bytes(m) + 512;
+    CenterWs o;
+    o.keys = L.take<u64>((size_t)m);
+    o.vals = L.take<uint32_t>((size_t)m);
+    o.sort = ws_nest(L, sort_ws, m);
+    L.pad(256);
+    return o;
+}
+
+extern "C" size_t ml3d_nearest_to_center_workspace_bytes(int64_t n_points) {
+    return n_points < 0 ? 0 : ws_bytes_of(center_ws, n_points);
 }
 
 static int nearest_to_center_impl(const float* points, int64_t n_points, const float* center_host, const float* center_dev,
@@ -787,19 +791,15 @@ static int nearest_to_center_impl(const float* points, int64_t n_points, const f
     if (n_points < 0 || k < 0 || k > n_points || (!center_host && !center_dev) || n_points > 0x7ffffff0ll) return ML3D_E_INVALID;
     if (k == 0) return 0;
     if (!points || !out_index) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_nearest_to_center_workspace_bytes(n_points)) return ML3D_E_WORKSPACE;
+    CenterWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, center_ws, n_points)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    u64* keys = (u64*)p;            p += (sizeof(u64) * (size_t)n_points + 255) & ~(size_t)255;
-    uint32_t* vals = (uint32_t*)p;  p += (sizeof(uint32_t) * (size_t)n_points + 255) & ~(size_t)255;
-    SortWs sw;
-    if (!sort_ws_carve(p, sort_ws_bytes(n_points), n_points, &sw)) return ML3D_E_WORKSPACE;
     hipLaunchKernelGGL(center_keys, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, st, points, n_points,
                        center_host ? (double)center_host[0] : 0.0, center_host ? (double)center_host[1] : 0.0,
-                       center_host ? (double)center_host[2] : 0.0, center_dev, keys, vals);
+                       center_host ? (double)center_host[2] : 0.0, center_dev, W.keys, W.vals);
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    if (sort_pairs_u64(keys, vals, n_points, 64, sw, st)) return ML3D_E_LAUNCH;
-    hipLaunchKernelGGL(center_take, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, keys, vals, k, out_index, out_dist2);
+    if (sort_pairs_u64(W.keys, W.vals, n_points, 64, W.sort, st)) return ML3D_E_LAUNCH;
+    hipLaunchKernelGGL(center_take, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, W.keys, W.vals, k, out_index, out_dist2);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 

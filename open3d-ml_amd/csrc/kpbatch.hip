@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include "ml3d_hip.h"
+#include "workspace.h"
 
 namespace ml3d {
 
@@ -50,8 +51,6 @@ kpb_lens_to_splits(const int64_t* __restrict__ len, int batch, int64_t* __restri
     for (int b = b0; b < b1; ++b) { run += len[b]; splits[b + 1] = run; }
 }
 
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace ml3d
 
 using namespace ml3d;
@@ -66,34 +65,39 @@ struct KpbSet {
     float* rot_out;                      // the pooled points in that orientation [n, 3]
 };
 
-static size_t kpb_set_bytes(int64_t n0, int64_t batch, int cap) {
-    return al256(ml3d_radius_dense_workspace_bytes(n0, n0, batch, cap)) * 2 + al256(ml3d_subsample_workspace_bytes(n0, batch)) +
-           2 * al256(sizeof(float) * 3 * (size_t)n0);
+// two scratch sets + per layer: row splits int64[batch + 1], the device-side size record int64[8 + batch]
+struct KpbWs {
+    KpbSet S[2];
+    int64_t* splits[ML3D_KPBATCH_MAX_LAYERS];
+    int64_t* rec[ML3D_KPBATCH_MAX_LAYERS];     // device size record of sync l: [conv 2][sub 2][pool(l-1) 2][up(l-1) 2][lengths(l+1) batch]
+};
+static KpbWs kpb_ws(WsLayout& lay, int64_t n0, int64_t batch, int num_layers, int cap) {
+    const size_t rwb = ws_up(ml3d_radius_dense_workspace_bytes(n0, n0, batch, cap));
+    const size_t swb = ws_up(ml3d_subsample_workspace_bytes(n0, batch));
+    KpbWs o;
+    for (KpbSet& S : o.S) {
+        S.conv_ws = lay.take<char>(rwb); S.conv_wsb = rwb;
+        S.up_ws = lay.take<char>(rwb);   S.up_wsb = rwb;
+        S.sub_ws = lay.take<char>(swb);  S.sub_wsb = swb;
+        S.rot_in = lay.take<float>(3 * (size_t)n0);
+        S.rot_out = lay.take<float>(3 * (size_t)n0);
+    }
+    for (int l = 0; l < num_layers; ++l) o.splits[l] = lay.take<int64_t>((size_t)(batch + 1));
+    for (int l = 0; l < num_layers; ++l) o.rec[l] = lay.take<int64_t>((size_t)(8 + batch));
+    lay.pad(768);
+    return o;
 }
 
 extern "C" size_t ml3d_kpconv_batch_workspace_bytes(int64_t n_points, int64_t batch, int num_layers, int cap) {
     if (n_points < 0 || batch <= 0 || num_layers <= 0 || num_layers > ML3D_KPBATCH_MAX_LAYERS || cap <= 0) return 0;
     if (ml3d_radius_dense_workspace_bytes(n_points, n_points, batch, cap) == 0) return 0;
-    // two scratch sets + per layer: row splits int64[batch + 1], the device-side size record int64[8 + batch]
-    return 2 * kpb_set_bytes(n_points, batch, cap) +
-           (size_t)num_layers * (al256(8 * (size_t)(batch + 1)) + al256(8 * (size_t)(8 + batch))) + 1024;
+    return ws_bytes_of(kpb_ws, n_points, batch, num_layers, cap);
 }
 
 extern "C" size_t ml3d_kpconv_batch_host_scratch_bytes(int64_t batch, int num_layers) {
     if (batch <= 0 || num_layers <= 0) return 0;
     return 8 * (size_t)(8 + batch) + 8 * (size_t)(batch + 1);          // one size record + the staging of layer 0's row splits
 }
-
-namespace {
-struct Bump {
-    char* base; size_t cap; size_t used;
-    void* take(size_t bytes) {       // nullptr when the arena is too small (`used` still advances: the caller learns the need)
-        const size_t at = al256(used);
-        used = at + bytes;
-        return used <= cap ? base + at : nullptr;
-    }
-};
-}  // namespace
 
 extern "C" int ml3d_kpconv_batch_build(const float* points, const int64_t* lengths_host, int64_t batch, int64_t n_points,
                                        const ML3DKpBatchDesc* desc, const float* const* rotations, void* arena,
@@ -105,34 +109,22 @@ extern "C" int ml3d_kpconv_batch_build(const float* points, const int64_t* lengt
     for (int l = 0; l < L; ++l)
         if (!(desc->radius[l] > 0.f) || (l + 1 < L && !(desc->dl[l] > 0.f))) return ML3D_E_INVALID;
     if (n_points > 0 && !points) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_kpconv_batch_workspace_bytes(n_points, batch, L, cap) || !workspace) return ML3D_E_WORKSPACE;
+    KpbWs carved;
+    if (!ws_carve(workspace, workspace_bytes, &carved, kpb_ws, n_points, batch, L, cap) || !workspace) return ML3D_E_WORKSPACE;
     if (host_scratch_bytes < ml3d_kpconv_batch_host_scratch_bytes(batch, L) || !host_scratch) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     memset(out, 0, sizeof(*out));
     out->num_layers = L;
 
-    // ---- carve the workspace ---------------------------------------------------------------------------------------------------
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    KpbSet S[2];
-    const size_t rwb = al256(ml3d_radius_dense_workspace_bytes(n_points, n_points, batch, cap));
-    const size_t swb = al256(ml3d_subsample_workspace_bytes(n_points, batch));
-    const size_t pb = al256(sizeof(float) * 3 * (size_t)n_points);
-    for (int k = 0; k < 2; ++k) {
-        S[k].conv_ws = p; S[k].conv_wsb = rwb; p += rwb;
-        S[k].up_ws = p;   S[k].up_wsb = rwb;   p += rwb;
-        S[k].sub_ws = p;  S[k].sub_wsb = swb;  p += swb;
-        S[k].rot_in = (float*)p;  p += pb;
-        S[k].rot_out = (float*)p; p += pb;
-    }
-    int64_t* splits[ML3D_KPBATCH_MAX_LAYERS];
-    int64_t* rec[ML3D_KPBATCH_MAX_LAYERS];     // device size record of sync l: [conv 2][sub 2][pool(l-1) 2][up(l-1) 2][lengths(l+1) batch]
-    for (int l = 0; l < L; ++l) { splits[l] = (int64_t*)p; p += al256(8 * (size_t)(batch + 1)); }
-    for (int l = 0; l < L; ++l) { rec[l] = (int64_t*)p;    p += al256(8 * (size_t)(8 + batch)); }
+    KpbSet* const S = carved.S;
+    int64_t* const* const splits = carved.splits;
+    int64_t* const* const rec = carved.rec;
     const size_t rec_n = (size_t)(8 + batch);
     int64_t* hrec = (int64_t*)host_scratch;
     int64_t* hsplits = hrec + rec_n;            // staging of layer 0's row splits (read by the copy engine: never reused in this call)
 
-    Bump A = {(char*)arena, arena ? arena_bytes : 0, 0};
+    // the arena: a walker that keeps counting when it runs out, so the caller learns the need (arena_used)
+    WsLayout A(arena, arena_bytes);
 
     // ---- layer 0: the caller's points; its row splits from the host lengths (the one upload of the build) -----------------------
     {
@@ -213,15 +205,15 @@ extern "C" int ml3d_kpconv_batch_build(const float* points, const int64_t* lengt
             ML3DKpLayerOut& Q = out->layer[l - 1];
             Q.pool_cols = hrec[5]; Q.up_cols = hrec[7];
             if (n[l] > 0 && Q.pool_cols > 0) {
-                int32_t* m = (int32_t*)A.take(4 * (size_t)n[l] * (size_t)Q.pool_cols);
-                if (!m) { out->arena_used = (int64_t)A.used; return ML3D_E_WORKSPACE; }
+                int32_t* m = A.take<int32_t>((size_t)n[l] * (size_t)Q.pool_cols);
+                if (!m) { out->arena_used = (int64_t)A.bytes(); return ML3D_E_WORKSPACE; }
                 rc = ml3d_radius_dense_expand(n[l - 1], n[l], batch, cap, Q.pool_cols, (int32_t)n[l - 1], m, V.conv_ws, V.conv_wsb, st);
                 if (rc) return rc;
                 Q.pool_offset = (int64_t)((char*)m - (char*)arena);
             }
             if (n[l - 1] > 0 && Q.up_cols > 0) {
-                int32_t* m = (int32_t*)A.take(4 * (size_t)n[l - 1] * (size_t)Q.up_cols);
-                if (!m) { out->arena_used = (int64_t)A.used; return ML3D_E_WORKSPACE; }
+                int32_t* m = A.take<int32_t>((size_t)n[l - 1] * (size_t)Q.up_cols);
+                if (!m) { out->arena_used = (int64_t)A.bytes(); return ML3D_E_WORKSPACE; }
                 rc = ml3d_radius_dense_expand(n[l], n[l - 1], batch, cap, Q.up_cols, (int32_t)n[l], m, V.up_ws, V.up_wsb, st);
                 if (rc) return rc;
                 Q.up_offset = (int64_t)((char*)m - (char*)arena);
@@ -230,8 +222,8 @@ extern "C" int ml3d_kpconv_batch_build(const float* points, const int64_t* lengt
         if (desc->has_conv[l]) {
             O.conv_cols = hrec[1];
             if (n[l] > 0 && O.conv_cols > 0) {
-                int32_t* m = (int32_t*)A.take(4 * (size_t)n[l] * (size_t)O.conv_cols);
-                if (!m) { out->arena_used = (int64_t)A.used; return ML3D_E_WORKSPACE; }
+                int32_t* m = A.take<int32_t>((size_t)n[l] * (size_t)O.conv_cols);
+                if (!m) { out->arena_used = (int64_t)A.bytes(); return ML3D_E_WORKSPACE; }
                 mark(l, 2);
                 rc = ml3d_radius_dense_expand(n[l], n[l], batch, cap, O.conv_cols, (int32_t)n[l], m, W.conv_ws, W.conv_wsb, st);
                 if (rc) return rc;
@@ -246,8 +238,8 @@ extern "C" int ml3d_kpconv_batch_build(const float* points, const int64_t* lengt
         const int64_t m_next = hrec[2];
         n[l + 1] = m_next;
         for (int64_t b = 0; b < batch; ++b) out_lengths_host[(size_t)(l + 1) * (size_t)batch + b] = (int32_t)hrec[8 + b];
-        float* pool_p = (float*)A.take(sizeof(float) * 3 * (size_t)m_next);
-        if (!pool_p) { out->arena_used = (int64_t)A.used; return ML3D_E_WORKSPACE; }
+        float* pool_p = A.take<float>(3 * (size_t)m_next);
+        if (!pool_p) { out->arena_used = (int64_t)A.bytes(); return ML3D_E_WORKSPACE; }
         hipLaunchKernelGGL(kpb_lens_to_splits, dim3(1), dim3(256), 0, st, rec[l] + 8, (int)batch, splits[l + 1]);
         if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
         const bool rot = rotations && rotations[l];
@@ -278,6 +270,6 @@ extern "C" int ml3d_kpconv_batch_build(const float* points, const int64_t* lengt
         rc = phase_a(l + 1);                               // the next layer's conv search + subsampling count, other scratch set
         if (rc) return rc;
     }
-    out->arena_used = (int64_t)A.used;
+    out->arena_used = (int64_t)A.bytes();
     return 0;
 }

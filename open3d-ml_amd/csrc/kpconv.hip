@@ -846,7 +846,16 @@ static int launch_weighted(const KpArgs& a, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
-static inline size_t kp_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// [wf float [nq][KP_K][cin] | the GEMM's split-K partials, the larger of the two paths' needs]
+struct KpWs { float* wf; char* partial; };
+static KpWs kp_ws(WsLayout& L, int64_t n_queries, int cin, int cout) {
+    const size_t p32 = gemm_partial_bytes(n_queries, cout, KP_K * cin), pbf = gemm_partial_bytes_bf16x3(n_queries, cout, KP_K * cin);
+    KpWs o;
+    o.wf = L.take<float>((size_t)(n_queries > 0 ? n_queries : 1) * KP_K * (size_t)cin);
+    o.partial = L.take<char>(p32 > pbf ? p32 : pbf);
+    L.pad(256);
+    return o;
+}
 
 }  // namespace ml3d
 
@@ -854,10 +863,7 @@ using namespace ml3d;
 
 extern "C" size_t ml3d_kpconv_workspace_bytes(int64_t n_queries, int cin, int cout, int num_kernel_points) {
     if (n_queries < 0 || cin <= 0 || cout <= 0 || num_kernel_points != KP_K) return 0;
-    size_t b = kp_align(sizeof(float) * (size_t)(n_queries > 0 ? n_queries : 1) * KP_K * (size_t)cin);
-    const size_t p32 = gemm_partial_bytes(n_queries, cout, KP_K * cin), pbf = gemm_partial_bytes_bf16x3(n_queries, cout, KP_K * cin);
-    b += kp_align(p32 > pbf ? p32 : pbf);
-    return b + 512;
+    return ws_bytes_of(kp_ws, n_queries, cin, cout);
 }
 
 static int kpconv_run(const float* q_pts, const float* s_pts, const int32_t* neighb_inds, int64_t n_queries,
@@ -873,18 +879,16 @@ static int kpconv_run(const float* q_pts, const float* s_pts, const int32_t* nei
     if (n_queries == 0) return 0;
     if (!q_pts || !kernel_points || !weights || !out || (max_neighbors > 0 && (!neighb_inds || !features || !s_pts)))
         return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_kpconv_workspace_bytes(n_queries, cin, cout, num_kernel_points)) return ML3D_E_WORKSPACE;
+    KpWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, kp_ws, n_queries, cin, cout)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = ws_align(workspace);
-    float* wf = (float*)p;
-    p += kp_align(sizeof(float) * (size_t)n_queries * KP_K * (size_t)cin);
     KpArgs a;
     a.q_pts = q_pts; a.s_pts = s_pts; a.inds = neighb_inds; a.nq = n_queries; a.ns = n_supports; a.h = (int)max_neighbors;
     a.x = features; a.cin = cin; a.kp = kernel_points;
     a.inv_extent = 1.0f / kp_extent; a.influence = kp_influence_mode;
     const float sigma = kp_extent * 0.3f;                       // kpconv.py:1122-1125 + radius_gaussian eps
     a.gauss_den = 2.0f * sigma * sigma + 1e-9f;
-    a.wf = wf;
+    a.wf = W.wf;
     a.off = offset_features; a.off_dim = offset_dim; a.extent = kp_extent;
     a.c_total = cin; a.c_off = 0;
     const KpOut ko = {weights, bias, act, slope, cout, out};
@@ -909,17 +913,17 @@ static int kpconv_run(const float* q_pts, const float* s_pts, const int32_t* nei
     int rc = launch_weighted(a, st);
     if (rc) return rc;
     RowsA A;
-    A.a = wf; A.lda = (int64_t)KP_K * cin; A.k1 = KP_K * cin;
+    A.a = W.wf; A.lda = (int64_t)KP_K * cin; A.k1 = KP_K * cin;
     A.gather = nullptr; A.gather_stride = 0; A.a_rows = n_queries;
     A.a2 = nullptr; A.lda2 = 0; A.k2 = 0;
     A.gather_on_a2 = 0; A.g_rows_per_item = 0; A.g_src_rows_per_item = 0;
     const Epilogue ep = Epilogue::of(bias, act, slope);
     if (packed) {           // the contraction on the bf16 matrix pipe (gemm.h: three-way split of both operands); ineligible -> f32 below
-        const int rcb = gemm_rows_bf16x3(wf, (int64_t)KP_K * cin, KP_K * cin, nullptr, 0, 0, n_queries, packed, cout, ep, out, cout, p,
+        const int rcb = gemm_rows_bf16x3(W.wf, (int64_t)KP_K * cin, KP_K * cin, nullptr, 0, 0, n_queries, packed, cout, ep, out, cout, W.partial,
                                          gemm_partial_bytes_bf16x3(n_queries, cout, KP_K * cin), st);
         if (rcb != ML3D_E_UNSUPPORTED) return rcb;
     }
-    return gemm_rows(A, weights, n_queries, cout, KP_K * cin, ep, out, cout, p,
+    return gemm_rows(A, weights, n_queries, cout, KP_K * cin, ep, out, cout, W.partial,
                      gemm_partial_bytes(n_queries, cout, KP_K * cin), st);
 }
 

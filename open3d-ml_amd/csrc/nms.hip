@@ -620,18 +620,55 @@ topk_sort(const u64* __restrict__ sel, int k, int kp2, int64_t* __restrict__ out
     }
 }
 
-static inline size_t nms_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// ---- workspace layouts (workspace.h), one per op ---------------------------------------------------------------------------------------
+struct NmsWs { u64* keys; uint32_t* order; u64* mask; SortWs sort; };       // mask [n][words]
+static NmsWs nms_ws(WsLayout& L, int64_t n) {
+    const int64_t m = n > 0 ? n : 1;
+    NmsWs o;
+    o.keys = L.take<u64>((size_t)m);
+    o.order = L.take<uint32_t>((size_t)m);
+    o.mask = L.take<u64>((size_t)(m * ((m + 63) / 64)));
+    o.sort = ws_nest(L, sort_ws, m);
+    L.pad(256);
+    return o;
+}
+
+struct TopkWs { int *tables, *counters; u64* sel; };
+// tables [rows][3][TOPK_BINS] and counters [rows][2] are ONE piece: the op zeroes both with one fill
+static TopkWs topk_ws(WsLayout& L, int64_t rows, int64_t k) {
+    const size_t R = (size_t)(rows > 0 ? rows : 1);
+    TopkWs o;
+    o.tables = L.take<int>(R * (3 * TOPK_BINS + 2));
+    o.counters = o.tables ? o.tables + R * 3 * TOPK_BINS : nullptr;
+    o.sel = L.take<u64>(R * (size_t)(k > 0 ? k : 1));
+    L.pad(256);
+    return o;
+}
+
+struct PpBoxesWs { uint32_t* order; int32_t* nvalid; u64* mask; int32_t *keep, *count; float *box, *bev, *score; int32_t* dirbit; };
+static PpBoxesWs pp_boxes_ws(WsLayout& L, int64_t batch, int64_t k, int num_classes) {
+    const size_t B = (size_t)(batch > 0 ? batch : 1), P = B * (size_t)num_classes, n = (size_t)(k > 0 ? k : 1);
+    const size_t words = (n + 63) / 64;
+    PpBoxesWs o;
+    o.order = L.take<uint32_t>(P * n);
+    o.nvalid = L.take<int32_t>(P);
+    o.mask = L.take<u64>(P * n * words);
+    o.keep = L.take<int32_t>(P * n);
+    o.count = L.take<int32_t>(P);
+    o.box = L.take<float>(7 * B * n);
+    o.bev = L.take<float>(5 * B * n);
+    o.score = L.take<float>(P * n);
+    o.dirbit = L.take<int32_t>(B * n);
+    L.pad(256);
+    return o;
+}
 
 }  // namespace ml3d
 
 using namespace ml3d;
 
 extern "C" size_t ml3d_nms_workspace_bytes(int64_t n) {
-    if (n < 0) return 0;
-    const int64_t m = n > 0 ? n : 1;
-    const int64_t words = (m + 63) / 64;
-    return nms_align(sizeof(u64) * (size_t)m) + nms_align(sizeof(uint32_t) * (size_t)m) +
-           nms_align(sizeof(u64) * (size_t)(m * words)) + sort_ws_bytes(m) + 512;
+    return n < 0 ? 0 : ws_bytes_of(nms_ws, n);
 }
 
 extern "C" int ml3d_nms(const float* boxes, const float* scores, int64_t n, float iou_threshold, int64_t* out_keep,
@@ -641,22 +678,17 @@ extern "C" int ml3d_nms(const float* boxes, const float* scores, int64_t n, floa
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { (void)hipMemsetAsync(out_count, 0, sizeof(int64_t), st); return 0; }
     if (!boxes || !scores || !out_keep) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_nms_workspace_bytes(n)) return ML3D_E_WORKSPACE;
+    NmsWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, nms_ws, n)) return ML3D_E_WORKSPACE;
     const int words = (int)((n + 63) / 64);
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    u64* keys = (u64*)p;            p += nms_align(sizeof(u64) * (size_t)n);
-    uint32_t* order = (uint32_t*)p; p += nms_align(sizeof(uint32_t) * (size_t)n);
-    u64* mask = (u64*)p;            p += nms_align(sizeof(u64) * (size_t)(n * words));
-    SortWs sw;
-    if (!sort_ws_carve(p, sort_ws_bytes(n), n, &sw)) return ML3D_E_WORKSPACE;
-    hipLaunchKernelGGL(nms_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scores, n, keys, order);
+    hipLaunchKernelGGL(nms_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scores, n, W.keys, W.order);
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    if (sort_pairs_u64(keys, order, n, 64, sw, st)) return ML3D_E_LAUNCH;
-    zero_async(mask, sizeof(u64) * (size_t)(n * words), st);
+    if (sort_pairs_u64(W.keys, W.order, n, 64, W.sort, st)) return ML3D_E_LAUNCH;
+    zero_async(W.mask, sizeof(u64) * (size_t)(n * words), st);
     hipLaunchKernelGGL(nms_mask, dim3((unsigned)words, (unsigned)(n < 32768 ? n : 32768), (unsigned)((n + 32767) / 32768)), dim3(64), 0, st,
-                       boxes, order, n, iou_threshold, words, mask);
+                       boxes, W.order, n, iou_threshold, words, W.mask);
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    hipLaunchKernelGGL(nms_reduce, dim3(1), dim3(64), 0, st, mask, order, n, words, out_keep, out_count);
+    hipLaunchKernelGGL(nms_reduce, dim3(1), dim3(64), 0, st, W.mask, W.order, n, words, out_keep, out_count);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
@@ -673,8 +705,7 @@ extern "C" int ml3d_pp_anchor_scores(const float* cls, const int64_t* cls_stride
 
 extern "C" size_t ml3d_topk_rows_workspace_bytes(int64_t rows, int64_t n, int64_t k) {
     if (rows < 0 || n < 0 || k < 0 || k > n || k > NMSB_MAX) return 0;
-    const size_t R = (size_t)(rows > 0 ? rows : 1);
-    return nms_align(4 * R * (3 * TOPK_BINS + 2)) /* tables + counters */ + nms_align(8 * R * (size_t)(k > 0 ? k : 1)) /* sel */ + 512;
+    return ws_bytes_of(topk_ws, rows, k);
 }
 
 extern "C" int ml3d_topk_rows(const float* values, int64_t rows, int64_t n, int64_t k, int64_t* out_index, float* out_value,
@@ -683,32 +714,23 @@ extern "C" int ml3d_topk_rows(const float* values, int64_t rows, int64_t n, int6
     if (k > NMSB_MAX) return ML3D_E_UNSUPPORTED;
     if (rows == 0 || k == 0) return 0;
     if (!values || !out_index || !workspace) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_topk_rows_workspace_bytes(rows, n, k)) return ML3D_E_WORKSPACE;
+    TopkWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, topk_ws, rows, k)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int* tables = (int*)p;
-    int* counters = tables + (size_t)rows * 3 * TOPK_BINS;
-    p += nms_align(4 * (size_t)rows * (3 * TOPK_BINS + 2));
-    u64* sel = (u64*)p;
-    zero_async(tables, 4 * (size_t)rows * (3 * TOPK_BINS + 2), st);        // (a fill kernel, not hipMemsetAsync: grid.h)
+    zero_async(W.tables, 4 * (size_t)rows * (3 * TOPK_BINS + 2), st);        // (a fill kernel, not hipMemsetAsync: grid.h)
     const dim3 grid((unsigned)((n + TOPK_CHUNK - 1) / TOPK_CHUNK), (unsigned)rows);
     for (int level = 0; level < 3; ++level)
-        hipLaunchKernelGGL(ml3d::topk_hist, grid, dim3(256), 0, st, values, n, (int)k, level, tables);
-    hipLaunchKernelGGL(ml3d::topk_take, grid, dim3(256), 0, st, values, n, (int)k, tables, counters, sel);
+        hipLaunchKernelGGL(ml3d::topk_hist, grid, dim3(256), 0, st, values, n, (int)k, level, W.tables);
+    hipLaunchKernelGGL(ml3d::topk_take, grid, dim3(256), 0, st, values, n, (int)k, W.tables, W.counters, W.sel);
     int kp2 = 1;
     while (kp2 < k) kp2 <<= 1;
-    hipLaunchKernelGGL(ml3d::topk_sort, dim3((unsigned)rows), dim3(256), 0, st, sel, (int)k, kp2, out_index, out_value, values, n);
+    hipLaunchKernelGGL(ml3d::topk_sort, dim3((unsigned)rows), dim3(256), 0, st, W.sel, (int)k, kp2, out_index, out_value, values, n);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
 extern "C" size_t ml3d_pp_boxes_workspace_bytes(int64_t batch, int64_t k, int num_classes) {
     if (batch < 0 || k < 0 || num_classes <= 0 || k > NMSB_MAX) return 0;
-    const size_t P = (size_t)(batch > 0 ? batch : 1) * (size_t)num_classes, n = (size_t)(k > 0 ? k : 1);
-    const size_t words = (n + 63) / 64;
-    return nms_align(4 * P * n) /* order */ + nms_align(4 * P) /* nvalid */ + nms_align(8 * P * n * words) /* mask */ +
-           nms_align(4 * P * n) /* keep */ + nms_align(4 * P) /* count */ + nms_align(4 * 7 * (P / num_classes) * n) /* box */ +
-           nms_align(4 * 5 * (P / num_classes) * n) /* bev */ + nms_align(4 * P * n) /* score */ +
-           nms_align(4 * (P / num_classes) * n) /* dir */ + 512;
+    return ws_bytes_of(pp_boxes_ws, batch, k, num_classes);
 }
 
 extern "C" int ml3d_pp_boxes(const float* cls, const float* reg, const float* dir, const int64_t* strides9,
@@ -723,26 +745,17 @@ extern "C" int ml3d_pp_boxes(const float* cls, const float* reg, const float* di
     if (!cls || !reg || !dir || !strides9 || !anchors || !candidates || !out_rows) return ML3D_E_INVALID;
     const ml3d::HeadMap mc = {cls, strides9[0], strides9[1], strides9[2]}, mr = {reg, strides9[3], strides9[4], strides9[5]},
                         md = {dir, strides9[6], strides9[7], strides9[8]};
-    if (workspace_bytes < ml3d_pp_boxes_workspace_bytes(batch, k, num_classes)) return ML3D_E_WORKSPACE;
+    PpBoxesWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, pp_boxes_ws, batch, k, num_classes)) return ML3D_E_WORKSPACE;
     const int64_t P = batch * num_classes;
     const int words = (int)((k + 63) / 64);
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    uint32_t* order = (uint32_t*)p;  p += nms_align(4 * (size_t)(P * k));
-    int32_t* nvalid = (int32_t*)p;   p += nms_align(4 * (size_t)P);
-    u64* mask = (u64*)p;             p += nms_align(8 * (size_t)(P * k * words));
-    int32_t* keep = (int32_t*)p;     p += nms_align(4 * (size_t)(P * k));
-    int32_t* count = (int32_t*)p;    p += nms_align(4 * (size_t)P);
-    float* box = (float*)p;          p += nms_align(4 * 7 * (size_t)(batch * k));
-    float* bev = (float*)p;          p += nms_align(4 * 5 * (size_t)(batch * k));
-    float* score = (float*)p;        p += nms_align(4 * (size_t)(P * k));
-    int32_t* dirbit = (int32_t*)p;
     hipLaunchKernelGGL(ml3d::pp_decode, dim3((unsigned)((batch * k + 255) / 256)), dim3(256), 0, st, mc, mr, md,
-                       anchors, candidates, batch, k, num_anchors, num_classes, hw, box, bev, score, dirbit);
-    hipLaunchKernelGGL(ml3d::nmsb_order, dim3((unsigned)P), dim3(256), 0, st, score, k, score_threshold, order, nvalid);
-    hipLaunchKernelGGL(ml3d::nmsb_mask, dim3((unsigned)words, (unsigned)k, (unsigned)P), dim3(64), 0, st, bev, order, nvalid,
-                       k, num_classes, iou_threshold, words, mask);
-    hipLaunchKernelGGL(ml3d::nmsb_reduce, dim3((unsigned)P), dim3(64), 0, st, mask, order, nvalid, k, words, keep, count);
-    hipLaunchKernelGGL(ml3d::pp_collect, dim3((unsigned)((P * k + 255) / 256)), dim3(256), 0, st, box, score, dirbit, keep, count,
+                       anchors, candidates, batch, k, num_anchors, num_classes, hw, W.box, W.bev, W.score, W.dirbit);
+    hipLaunchKernelGGL(ml3d::nmsb_order, dim3((unsigned)P), dim3(256), 0, st, W.score, k, score_threshold, W.order, W.nvalid);
+    hipLaunchKernelGGL(ml3d::nmsb_mask, dim3((unsigned)words, (unsigned)k, (unsigned)P), dim3(64), 0, st, W.bev, W.order, W.nvalid,
+                       k, num_classes, iou_threshold, words, W.mask);
+    hipLaunchKernelGGL(ml3d::nmsb_reduce, dim3((unsigned)P), dim3(64), 0, st, W.mask, W.order, W.nvalid, k, words, W.keep, W.count);
+    hipLaunchKernelGGL(ml3d::pp_collect, dim3((unsigned)((P * k + 255) / 256)), dim3(256), 0, st, W.box, W.score, W.dirbit, W.keep, W.count,
                        batch, k, num_classes, dir_offset, out_rows, out_total);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

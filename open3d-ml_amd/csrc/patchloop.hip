@@ -336,7 +336,6 @@ sb_emit(SbItems it, const float* __restrict__ sph, const int32_t* __restrict__ r
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-static inline size_t pb_al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // the active clouds of a call, checked: splits monotone from 0, slots strictly ascending (so distinct) and inside [0, n_clouds),
 // every active cloud with at least min_len points.  Returns the points of the active clouds, < 0 on a bad argument.
@@ -392,14 +391,68 @@ static void pb_chunks(const int64_t* splits, const int32_t* active, int64_t n_ac
     }
 }
 
+// ---- workspace layouts (workspace.h), one per op ---------------------------------------------------------------------------------------
+struct ArgminWs { double* part_v; int* part_i; };      // [tiles] each: a tile's minimum and where it is
+static ArgminWs argmin_ws(WsLayout& L, int64_t n_points, int64_t n_clouds) {
+    const size_t tiles = (size_t)(n_points / PB_TILE + n_clouds + 1);
+    ArgminWs o;
+    o.part_v = L.take<double>(tiles);
+    o.part_i = L.take<int>(tiles);
+    L.pad(256);
+    return o;
+}
+
+// mx [n_active] bits of the largest float32 distance, mean [n_active][4] column means, d2 [n_active][k]; keys .. item_of [m]
+struct PatchBatchWs { unsigned* mx; float *mean, *d2; u64* keys; uint32_t *vals, *item_of; SortWs sort; };
+// mx, mean and d2 stay neighbours in this order: the op zeroes mx and mean with ONE fill, from mx up to d2
+static PatchBatchWs patch_batch_ws(WsLayout& L, int64_t n_points, int64_t n_active, int64_t k) {
+    const int64_t m = n_points > 0 ? n_points : 1;
+    PatchBatchWs o;
+    o.mx = L.take<unsigned>((size_t)n_active);
+    o.mean = L.take<float>(4 * (size_t)n_active);
+    o.d2 = L.take<float>((size_t)n_active * (size_t)k);
+    o.keys = L.take<u64>((size_t)m);
+    o.vals = L.take<uint32_t>((size_t)m);
+    o.item_of = L.take<uint32_t>((size_t)m);
+    o.sort = ws_nest(L, sort_ws, m);
+    L.pad(256);
+    return o;
+}
+
+struct SphereSelectWs { int* cnt; u64* keys; uint32_t* vals; SortWs sort; };      // cnt [n_active]: hits per item
+static SphereSelectWs sphere_select_ws(WsLayout& L, int64_t n_points, int64_t n_active) {
+    const int64_t m = n_points > 0 ? n_points : 1;
+    SphereSelectWs o;
+    o.cnt = L.take<int>((size_t)(n_active > 0 ? n_active : 1));
+    o.keys = L.take<u64>((size_t)m);
+    o.vals = L.take<uint32_t>((size_t)m);
+    o.sort = ws_nest(L, sort_ws, m);
+    L.pad(256);
+    return o;
+}
+
+// mx, mean as above; sph [n_in][3] p - centre, in the shuffle's order; d2, row_of [n_in]
+struct SphereBatchWs { unsigned* mx; float *mean, *sph, *d2; int32_t* row_of; };
+// mx, mean and sph stay neighbours in this order: the op zeroes mx and mean with ONE fill, from mx up to sph
+static SphereBatchWs sphere_batch_ws(WsLayout& L, int64_t n_items, int64_t n_in) {
+    const size_t a = (size_t)(n_items > 0 ? n_items : 1), n = (size_t)(n_in > 0 ? n_in : 1);
+    SphereBatchWs o;
+    o.mx = L.take<unsigned>(a);
+    o.mean = L.take<float>(4 * a);
+    o.sph = L.take<float>(3 * n);
+    o.d2 = L.take<float>(n);
+    o.row_of = L.take<int32_t>(n);
+    L.pad(256);
+    return o;
+}
+
 }  // namespace ml3d
 
 using namespace ml3d;
 
 extern "C" size_t ml3d_possibility_argmin_workspace_bytes(int64_t n_points, int64_t n_clouds) {
     if (n_points < 0 || n_clouds < 0) return 0;
-    const size_t tiles = (size_t)(n_points / PB_TILE + n_clouds + 1);
-    return pb_al(sizeof(double) * tiles) + pb_al(sizeof(int) * tiles) + 512;
+    return ws_bytes_of(argmin_ws, n_points, n_clouds);
 }
 
 extern "C" int ml3d_possibility_argmin(const double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
@@ -407,26 +460,20 @@ extern "C" int ml3d_possibility_argmin(const double* possibility, const int64_t*
                                        void* workspace, size_t workspace_bytes, void* stream) {
     const int64_t m = pb_check(cloud_row_splits_host, n_clouds, active_host, n_active, 1);
     if (m < 0 || !possibility || !out_index || !out_min || !workspace) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_possibility_argmin_workspace_bytes(m, n_active)) return ML3D_E_WORKSPACE;
+    ArgminWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, argmin_ws, m, n_active)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const size_t tiles = (size_t)(m / PB_TILE + n_active + 1);
-    char* p = ws_align(workspace);
-    double* part_v = (double*)p;  p += pb_al(sizeof(double) * tiles);
-    int* part_i = (int*)p;
     pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(pb_argmin_tiles, dim3((unsigned)((longest + PB_TILE - 1) / PB_TILE), (unsigned)count), dim3(256), 0, st,
-                           possibility, it, part_v, part_i);
-        hipLaunchKernelGGL(pb_argmin_final, dim3((unsigned)count), dim3(64), 0, st, part_v, part_i, it, out_index, out_min);
+                           possibility, it, W.part_v, W.part_i);
+        hipLaunchKernelGGL(pb_argmin_final, dim3((unsigned)count), dim3(64), 0, st, W.part_v, W.part_i, it, out_index, out_min);
     });
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
 extern "C" size_t ml3d_patch_batch_workspace_bytes(int64_t n_points, int64_t n_active, int64_t k) {
     if (n_points < 0 || n_active < 0 || k < 0) return 0;
-    const int64_t m = n_points > 0 ? n_points : 1;
-    return pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active) +      // per item: the maximum-distance word, the three means
-           pb_al(sizeof(float) * (size_t)n_active * (size_t)k) + pb_al(sizeof(u64) * (size_t)m) + 2 * pb_al(sizeof(uint32_t) * (size_t)m) +
-           sort_ws_bytes(m) + 512;
+    return ws_bytes_of(patch_batch_ws, n_points, n_active, k);
 }
 
 extern "C" int ml3d_patch_batch(const float* points, double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
@@ -439,51 +486,41 @@ extern "C" int ml3d_patch_batch(const float* points, double* possibility, const 
     if (m < 0 || n_active * k > 0x7ffffff0ll) return ML3D_E_INVALID;
     if (!points || !possibility || !center_index || !perm || !out_pts || !out_features || !out_sel || !out_row || !workspace)
         return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_patch_batch_workspace_bytes(m, n_active, k)) return ML3D_E_WORKSPACE;
+    PatchBatchWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, patch_batch_ws, m, n_active, k)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = ws_align(workspace);
-    unsigned* mx = (unsigned*)p;      p += pb_al(4 * (size_t)n_active);       // [n_active]     bits of the largest float32 distance
-    float* mean = (float*)p;          p += pb_al(16 * (size_t)n_active);      // [n_active][4]  column means
-    float* d2 = (float*)p;            p += pb_al(sizeof(float) * (size_t)n_active * (size_t)k);
-    u64* keys = (u64*)p;              p += pb_al(sizeof(u64) * (size_t)m);
-    uint32_t* vals = (uint32_t*)p;    p += pb_al(sizeof(uint32_t) * (size_t)m);
-    uint32_t* item_of = (uint32_t*)p; p += pb_al(sizeof(uint32_t) * (size_t)m);
-    SortWs sw;
-    if (!sort_ws_carve(p, sort_ws_bytes(m), m, &sw)) return ML3D_E_WORKSPACE;
-    zero_async(mx, pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active), st);      // (a fill kernel, not hipMemsetAsync: grid.h)
+    zero_async(W.mx, (size_t)((char*)W.d2 - (char*)W.mx), st);      // mx and mean (a fill kernel, not hipMemsetAsync: grid.h)
     const unsigned kblocks = (unsigned)((k + 255) / 256);
     pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(pb_keys, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, points, it, center_index,
-                           keys, vals, item_of);
+                           W.keys, W.vals, W.item_of);
     });
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
     // all points of the active clouds by distance to their own cloud's centre, then ONE stable pass by cloud: every cloud's
     // points end up contiguous (in the order of the active list) and ascending in (distance, index)
-    if (sort_pairs_u64(keys, vals, m, 64, sw, st)) return ML3D_E_LAUNCH;
-    const uint32_t* sorted = vals;
+    if (sort_pairs_u64(W.keys, W.vals, m, 64, W.sort, st)) return ML3D_E_LAUNCH;
+    const uint32_t* sorted = W.vals;
     if (n_active > 1) {
         int bits = 1;
         while ((1ll << bits) < n_active) ++bits;
-        hipLaunchKernelGGL(pb_item_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, vals, item_of, m, keys);
-        if (sort_pairs_u64(keys, vals, m, bits, sw, st, true)) return ML3D_E_LAUNCH;
-        if (sort_result_in_alt(m, bits)) sorted = sw.vals_alt;
+        hipLaunchKernelGGL(pb_item_keys, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, W.vals, W.item_of, m, W.keys);
+        if (sort_pairs_u64(W.keys, W.vals, m, bits, W.sort, st, true)) return ML3D_E_LAUNCH;
+        if (sort_result_in_alt(m, bits)) sorted = W.sort.vals_alt;
     }
     pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int) {
         hipLaunchKernelGGL(pb_gather, dim3(kblocks, (unsigned)count), dim3(256), 0, st, points, sorted, it, center_index, perm, k, out_pts,
-                           out_sel, out_row, d2, mx);
+                           out_sel, out_row, W.d2, W.mx);
     });
-    hipLaunchKernelGGL(pb_bump, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_row, d2, mx, k, possibility);
-    if (dims_mask) hipLaunchKernelGGL(pb_mean_seq, dim3((unsigned)n_active), dim3(256), 0, st, out_pts, k, mean);
-    hipLaunchKernelGGL(pb_apply, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_pts, k, dims_mask, mean, out_row, extra, n_extra,
+    hipLaunchKernelGGL(pb_bump, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_row, W.d2, W.mx, k, possibility);
+    if (dims_mask) hipLaunchKernelGGL(pb_mean_seq, dim3((unsigned)n_active), dim3(256), 0, st, out_pts, k, W.mean);
+    hipLaunchKernelGGL(pb_apply, dim3(kblocks, (unsigned)n_active), dim3(256), 0, st, out_pts, k, dims_mask, W.mean, out_row, extra, n_extra,
                        feat_bias, feat_scale, out_features);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
 extern "C" size_t ml3d_sphere_select_workspace_bytes(int64_t n_points, int64_t n_active) {
     if (n_points < 0 || n_active < 0) return 0;
-    const int64_t m = n_points > 0 ? n_points : 1;
-    return pb_al(4 * (size_t)(n_active > 0 ? n_active : 1)) + pb_al(sizeof(u64) * (size_t)m) + pb_al(sizeof(uint32_t) * (size_t)m) +
-           sort_ws_bytes(m) + 512;
+    return ws_bytes_of(sphere_select_ws, n_points, n_active);
 }
 
 extern "C" int ml3d_sphere_select(const float* points, const int64_t* cloud_row_splits_host, int64_t n_clouds,
@@ -493,27 +530,22 @@ extern "C" int ml3d_sphere_select(const float* points, const int64_t* cloud_row_
     if (!(radius >= 0.f)) return ML3D_E_INVALID;
     const int64_t m = pb_check(cloud_row_splits_host, n_clouds, active_host, n_active, 1);
     if (m < 0 || !points || !center_index || !out_index || !out_count || !workspace || out_capacity < m) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_sphere_select_workspace_bytes(m, n_active)) return ML3D_E_WORKSPACE;
+    SphereSelectWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, sphere_select_ws, m, n_active)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = ws_align(workspace);
-    int* cnt = (int*)p;               p += pb_al(4 * (size_t)n_active);       // [n_active]  hits per item
-    u64* keys = (u64*)p;              p += pb_al(sizeof(u64) * (size_t)m);
-    uint32_t* vals = (uint32_t*)p;    p += pb_al(sizeof(uint32_t) * (size_t)m);
-    SortWs sw;
-    if (!sort_ws_carve(p, sort_ws_bytes(m), m, &sw)) return ML3D_E_WORKSPACE;
-    zero_async(cnt, pb_al(4 * (size_t)n_active), st);
+    zero_async(W.cnt, ws_up(4 * (size_t)n_active), st);
     const float r2 = radius * radius;                                        // (ml3d_radius_fill's own bound)
     pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
         hipLaunchKernelGGL(ss_keys, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, points, it, center_index,
-                           r2, keys, vals, cnt);
+                           r2, W.keys, W.vals, W.cnt);
     });
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
     int bits = 32;
     while ((1ll << (bits - 32)) < n_active) ++bits;
-    if (sort_pairs_u64(keys, vals, m, bits, sw, st, true)) return ML3D_E_LAUNCH;
-    const uint32_t* sorted = sort_result_in_alt(m, bits) ? sw.vals_alt : vals;
+    if (sort_pairs_u64(W.keys, W.vals, m, bits, W.sort, st, true)) return ML3D_E_LAUNCH;
+    const uint32_t* sorted = sort_result_in_alt(m, bits) ? W.sort.vals_alt : W.vals;
     pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& it, int count, int longest) {
-        hipLaunchKernelGGL(ss_emit, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, sorted, it, cnt, out_index,
+        hipLaunchKernelGGL(ss_emit, dim3((unsigned)((longest + 255) / 256), (unsigned)count), dim3(256), 0, st, sorted, it, W.cnt, out_index,
                            out_count);
     });
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
@@ -521,8 +553,7 @@ extern "C" int ml3d_sphere_select(const float* points, const int64_t* cloud_row_
 
 extern "C" size_t ml3d_sphere_batch_workspace_bytes(int64_t n_items, int64_t n_in) {
     if (n_items < 0 || n_in < 0) return 0;
-    const size_t a = (size_t)(n_items > 0 ? n_items : 1), n = (size_t)(n_in > 0 ? n_in : 1);
-    return pb_al(4 * a) + pb_al(16 * a) + pb_al(12 * n) + 2 * pb_al(4 * n) + 512;
+    return ws_bytes_of(sphere_batch_ws, n_items, n_in);
 }
 
 extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const int64_t* cloud_row_splits_host, int64_t n_clouds,
@@ -546,15 +577,10 @@ extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const
         n_out += m;
     }
     if (n_in > 0x7ffffff0ll) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_sphere_batch_workspace_bytes(n_active, n_in)) return ML3D_E_WORKSPACE;
+    SphereBatchWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, sphere_batch_ws, n_active, n_in)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* p = ws_align(workspace);
-    unsigned* mx = (unsigned*)p;      p += pb_al(4 * (size_t)n_active);       // [n_active]     bits of the largest float32 distance
-    float* mean = (float*)p;          p += pb_al(16 * (size_t)n_active);      // [n_active][4]  column means
-    float* sph = (float*)p;           p += pb_al(12 * (size_t)n_in);          // [n_in][3]      p - centre, in the shuffle's order
-    float* d2 = (float*)p;            p += pb_al(4 * (size_t)n_in);
-    int32_t* row_of = (int32_t*)p;
-    zero_async(mx, pb_al(4 * (size_t)n_active) + pb_al(16 * (size_t)n_active), st);
+    zero_async(W.mx, (size_t)((char*)W.sph - (char*)W.mx), st);      // mx and mean
     int64_t in0 = 0, keep0 = 0, out0 = 0;
     pb_chunks(cloud_row_splits_host, active_host, n_active, [&](const PbItems& cl, int count, int max_len) {
         const int64_t first = cl.first;
@@ -576,13 +602,13 @@ extern "C" int ml3d_sphere_batch(const float* points, double* possibility, const
         }
         it.first = cl.first;
         const dim3 gn((unsigned)((max_n + 255) / 256), (unsigned)count), gm((unsigned)((max_m + 255) / 256), (unsigned)count);
-        hipLaunchKernelGGL(sb_gather, gn, dim3(256), 0, st, points, it, center_index, cand, perm, sph, row_of, d2, mx);
-        hipLaunchKernelGGL(sb_bump, gn, dim3(256), 0, st, it, row_of, d2, mx, possibility);
-        if (dims_mask) hipLaunchKernelGGL(sb_mean_seq, dim3((unsigned)count), dim3(256), 0, st, sph, it, mean);
+        hipLaunchKernelGGL(sb_gather, gn, dim3(256), 0, st, points, it, center_index, cand, perm, W.sph, W.row_of, W.d2, W.mx);
+        hipLaunchKernelGGL(sb_bump, gn, dim3(256), 0, st, it, W.row_of, W.d2, W.mx, possibility);
+        if (dims_mask) hipLaunchKernelGGL(sb_mean_seq, dim3((unsigned)count), dim3(256), 0, st, W.sph, it, W.mean);
         if (linear && n_extra)
             hipLaunchKernelGGL(sb_rescale, dim3((unsigned)(((int64_t)max_len * n_extra + 255) / 256), (unsigned)count), dim3(256), 0, st,
                                extra, it, n_extra, feat_bias, feat_scale);
-        hipLaunchKernelGGL(sb_emit, gm, dim3(256), 0, st, it, sph, row_of, mean, keep, dims_mask, extra, n_extra, out_pts, out_columns,
+        hipLaunchKernelGGL(sb_emit, gm, dim3(256), 0, st, it, W.sph, W.row_of, W.mean, keep, dims_mask, extra, n_extra, out_pts, out_columns,
                            out_sel, out_row);
     });
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;

@@ -240,7 +240,16 @@ head_to_nchw(const float* __restrict__ in, int64_t ld, int c0, int C, int64_t hw
     }
 }
 
-static inline size_t pl_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// two ping-pong [M, P, 2U] buffers for multi-layer PFNs (U the widest hidden layer), nothing for the single-layer case
+struct PfnWs { float* buf[2]; };
+static PfnWs pfn_ws(WsLayout& L, int64_t n_pillars, int max_num_points, int num_layers, const int32_t* units_host) {
+    size_t widest = 0;
+    for (int i = 0; i + 1 < num_layers; ++i) widest = 2 * (size_t)units_host[i] > widest ? 2 * (size_t)units_host[i] : widest;
+    PfnWs o;
+    for (float*& b : o.buf) b = L.take<float>((size_t)(n_pillars > 0 ? n_pillars : 1) * max_num_points * widest);
+    L.pad(256);
+    return o;
+}
 
 }  // namespace ml3d
 
@@ -249,13 +258,7 @@ using namespace ml3d;
 extern "C" size_t ml3d_pillar_features_workspace_bytes(int64_t n_pillars, int max_num_points, int num_layers,
                                                        const int32_t* units_host) {
     if (n_pillars < 0 || max_num_points <= 0 || num_layers <= 0 || !units_host) return 0;
-    size_t widest = 0;
-    for (int i = 0; i + 1 < num_layers; ++i) {
-        size_t wdt = 2 * (size_t)units_host[i];
-        widest = wdt > widest ? wdt : widest;
-    }
-    // two ping-pong [M, P, 2U] buffers for multi-layer PFNs, nothing for the single-layer case
-    return 2 * pl_align(sizeof(float) * (size_t)(n_pillars > 0 ? n_pillars : 1) * max_num_points * widest) + 512;
+    return ws_bytes_of(pfn_ws, n_pillars, max_num_points, num_layers, units_host);
 }
 
 extern "C" int ml3d_pillar_features(const float* points, int64_t point_stride, int in_channels,
@@ -274,14 +277,8 @@ extern "C" int ml3d_pillar_features(const float* points, int64_t point_stride, i
     zero_async(canvas, sizeof(float) * (size_t)batch * ny * nx * canvas_channels, st);        // (a fill kernel, not hipMemsetAsync: grid.h)
     if (n_pillars == 0) return 0;
     if (!points || !voxel_coords || !point_indices || !point_row_splits || !batch_splits) return ML3D_E_INVALID;
-    if (workspace_bytes < ml3d_pillar_features_workspace_bytes(n_pillars, max_num_points, num_layers, units_host))
-        return ML3D_E_WORKSPACE;
-    size_t widest = 0;
-    for (int i = 0; i + 1 < num_layers; ++i) widest = 2 * (size_t)units_host[i] > widest ? 2 * (size_t)units_host[i] : widest;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    float* buf[2];
-    buf[0] = (float*)p;
-    buf[1] = (float*)(p + pl_align(sizeof(float) * (size_t)n_pillars * max_num_points * widest));
+    PfnWs W;
+    if (!ws_carve(workspace, workspace_bytes, &W, pfn_ws, n_pillars, max_num_points, num_layers, units_host)) return ML3D_E_WORKSPACE;
     PfnArgs a;
     a.points = points; a.point_stride = point_stride; a.in_ch = in_channels;
     a.coords = voxel_coords; a.pidx = point_indices; a.prs = point_row_splits;
@@ -289,7 +286,7 @@ extern "C" int ml3d_pillar_features(const float* points, int64_t point_stride, i
     a.vx = vx; a.vy = vy; a.x_off = x_offset; a.y_off = y_offset; a.nx = nx; a.ny = ny;
     a.wt = weights_host[0]; a.bias = bias_host[0]; a.units = units_host[0];
     a.last = num_layers == 1 ? 1 : 0;
-    a.canvas = canvas; a.canvas_c = canvas_channels; a.xcat = buf[0];
+    a.canvas = canvas; a.canvas_c = canvas_channels; a.xcat = W.buf[0];
     static const bool v4_off = [] { const char* e = getenv("ML3D_PFN_V4"); return e && atoi(e) == 0; }();
     if (!v4_off && in_channels == 4 && point_stride == 4 && ((uintptr_t)points & 15) == 0 && num_layers == 1 && units_host[0] == 64 &&
         batch <= 60)
@@ -300,12 +297,12 @@ extern "C" int ml3d_pillar_features(const float* points, int64_t point_stride, i
     int cin = 2 * units_host[0];
     for (int l = 1; l < num_layers; ++l) {
         PfnNextArgs n;
-        n.xin = buf[(l - 1) & 1]; n.cin = cin;
+        n.xin = W.buf[(l - 1) & 1]; n.cin = cin;
         n.coords = voxel_coords; n.batch_splits = batch_splits; n.batch = (int)batch; n.n_pillars = n_pillars;
         n.P = max_num_points; n.nx = nx; n.ny = ny;
         n.wt = weights_host[l]; n.bias = bias_host[l]; n.units = units_host[l];
         n.last = l == num_layers - 1 ? 1 : 0;
-        n.canvas = canvas; n.canvas_c = canvas_channels; n.xcat = buf[l & 1];
+        n.canvas = canvas; n.canvas_c = canvas_channels; n.xcat = W.buf[l & 1];
         size_t sm = sizeof(float) * (size_t)max_num_points * cin;
         if (sm > 64 * 1024) return ML3D_E_UNSUPPORTED;
         hipLaunchKernelGGL(pfn_next, dim3((unsigned)n_pillars), dim3(64), sm, st, n);

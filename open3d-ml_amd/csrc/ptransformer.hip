@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "ml3d_hip.h"
+#include "workspace.h"
 
 typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -171,7 +172,7 @@ extern "C" int ml3d_furthest_point_sampling(const float* points, const int64_t* 
     FPS_CLASS(64, 12)
 #undef FPS_CLASS
     if (!workspace || workspace_bytes < ml3d_fps_workspace_bytes(n_points, batch)) return ML3D_E_WORKSPACE;
-    float* mind = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* mind = (float*)ml3d::ws_align(workspace);
     return fps_launch<0, FPS_LDS_J>(points, row_splits, new_row_splits, batch, out_index, mind, st);
 }
 

@@ -141,12 +141,14 @@ __global__ __launch_bounds__(256) void pv_segment_mean(const u64* __restrict__ k
     for (int e = 0; e < VEC; ++e) o[e] = __fdiv_rn(acc[e], d);
 }
 
-static inline size_t pv_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static int pv_key_bits(u64 max_key) {
-    int bits = 1;
-    while (bits < 64 && (max_key >> bits) != 0) ++bits;
-    return bits;
+struct AvgVoxWs { u64* keys; uint32_t* vals; SortWs sort; };      // (key, point) pairs [batch * n] and the sort's scratch
+static AvgVoxWs avg_vox_ws(WsLayout& L, int64_t m) {
+    AvgVoxWs o;
+    o.keys = L.take<u64>((size_t)m);
+    o.vals = L.take<uint32_t>((size_t)m);
+    o.sort = ws_nest(L, sort_ws, m);
+    L.pad(256);
+    return o;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -250,8 +252,7 @@ extern "C" int ml3d_pvcnn_voxel_coords(const float* coords, int64_t batch, int64
 
 extern "C" size_t ml3d_avg_voxelize_workspace_bytes(int64_t batch, int64_t n) {
     if (batch <= 0 || n <= 0) return 0;
-    const int64_t m = batch * n;
-    return pv_align(sizeof(u64) * (size_t)m) + pv_align(sizeof(uint32_t) * (size_t)m) + sort_ws_bytes(m) + 512;
+    return ws_bytes_of(avg_vox_ws, batch * n);
 }
 
 extern "C" int ml3d_avg_voxelize(const float* feat, int64_t ldf, int c, const int32_t* vox_index, int64_t batch, int64_t n, int r,
@@ -262,26 +263,22 @@ extern "C" int ml3d_avg_voxelize(const float* feat, int64_t ldf, int c, const in
     const int64_t total = batch * n;
     const int cells = r * r * r;
     if ((int64_t)batch * cells * ldg >= ((int64_t)1 << 40)) return ML3D_E_INVALID;
-    if (!workspace || workspace_bytes < ml3d_avg_voxelize_workspace_bytes(batch, n)) return ML3D_E_WORKSPACE;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    u64* keys = (u64*)p;            p += pv_align(sizeof(u64) * (size_t)total);
-    uint32_t* vals = (uint32_t*)p;  p += pv_align(sizeof(uint32_t) * (size_t)total);
-    SortWs sw;
-    if (!sort_ws_carve(p, sort_ws_bytes(total), total, &sw)) return ML3D_E_WORKSPACE;
+    AvgVoxWs W;
+    if (!workspace || !ws_carve(workspace, workspace_bytes, &W, avg_vox_ws, total)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const u64 invalid = (u64)batch * (u64)cells;
-    const int key_bits = pv_key_bits(invalid);
+    const int key_bits = key_bits_for(invalid);
     const unsigned nb = (unsigned)((total + 255) / 256);
     zero_async(grid, sizeof(float) * (size_t)batch * (size_t)cells * (size_t)ldg, st);
-    hipLaunchKernelGGL(pv_keys, dim3(nb), dim3(256), 0, st, vox_index, total, (int)n, cells, invalid, keys, vals);
+    hipLaunchKernelGGL(pv_keys, dim3(nb), dim3(256), 0, st, vox_index, total, (int)n, cells, invalid, W.keys, W.vals);
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-    if (sort_pairs_u64(keys, vals, total, key_bits, sw, st, true)) return ML3D_E_LAUNCH;
-    if (sort_result_in_alt(total, key_bits)) { keys = sw.keys_alt; vals = sw.vals_alt; }
+    if (sort_pairs_u64(W.keys, W.vals, total, key_bits, W.sort, st, true)) return ML3D_E_LAUNCH;
+    if (sort_result_in_alt(total, key_bits)) { W.keys = W.sort.keys_alt; W.vals = W.sort.vals_alt; }
     const bool vec = (c & 3) == 0 && (ldf & 3) == 0 && (ldg & 3) == 0 && (((uintptr_t)feat) & 15) == 0;
     const int cq = vec ? c / 4 : c;
     const unsigned ns = (unsigned)((total * cq + 255) / 256);
-    if (vec) hipLaunchKernelGGL((pv_segment_mean<4>), dim3(ns), dim3(256), 0, st, (const u64*)keys, (const uint32_t*)vals, total, invalid, feat, ldf, cq, grid, ldg);
-    else hipLaunchKernelGGL((pv_segment_mean<1>), dim3(ns), dim3(256), 0, st, (const u64*)keys, (const uint32_t*)vals, total, invalid, feat, ldf, cq, grid, ldg);
+    if (vec) hipLaunchKernelGGL((pv_segment_mean<4>), dim3(ns), dim3(256), 0, st, (const u64*)W.keys, (const uint32_t*)W.vals, total, invalid, feat, ldf, cq, grid, ldg);
+    else hipLaunchKernelGGL((pv_segment_mean<1>), dim3(ns), dim3(256), 0, st, (const u64*)W.keys, (const uint32_t*)W.vals, total, invalid, feat, ldf, cq, grid, ldg);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
@@ -324,7 +321,7 @@ extern "C" int ml3d_segment_max_rows(const float* x, int64_t ldx, int64_t batch,
     const int64_t chunks = (n + PV_MAX_ROWS - 1) / PV_MAX_ROWS;
     if (chunks > 65535) return ML3D_E_UNSUPPORTED;
     if (!workspace || workspace_bytes < ml3d_segment_max_rows_workspace_bytes(batch, n, c)) return ML3D_E_WORKSPACE;
-    float* part = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* part = (float*)ws_align(workspace);
     hipStream_t st = (hipStream_t)stream;
     const unsigned gx = (unsigned)((c + 255) / 256);
     hipLaunchKernelGGL(pv_colmax, dim3(gx, (unsigned)chunks, (unsigned)batch), dim3(256), 0, st, x, ldx, n, PV_MAX_ROWS, c, part,

@@ -344,20 +344,9 @@ __global__ void ragged_to_dense_k(const uint32_t* __restrict__ values, const int
     }
 }
 
-static inline size_t rad_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace ml3d
 
 using namespace ml3d;
-
-// workspace layout: [grid | counts int32 (nq + 1) | scan scratch | stats u64[2] | spill u64[total]]
-static size_t rad_fixed_bytes(int64_t n_points, int64_t n_queries, int64_t batch) {
-    size_t b = grid_ws_bytes(n_points, batch);
-    b += rad_align(sizeof(int) * (size_t)(n_queries + 2));
-    b += rad_align(sizeof(int) * (size_t)((n_queries + 1 + 1023) / 1024 + 2));
-    b += rad_align(16);
-    return b + 256;
-}
 
 struct RadWs {
     GridWs grid;
@@ -367,23 +356,23 @@ struct RadWs {
     u64* spill;
 };
 
-static bool rad_carve(void* ws, size_t bytes, int64_t n_points, int64_t n_queries, int64_t batch, RadWs* out) {
-    if (bytes < rad_fixed_bytes(n_points, n_queries, batch)) return false;
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    size_t gb = grid_ws_bytes(n_points, batch);
-    if (!grid_ws_carve(p, gb, n_points, batch, &out->grid)) return false;
-    p += rad_align(gb);
-    out->counts = (int*)p;       p += rad_align(sizeof(int) * (size_t)(n_queries + 2));
-    out->block_sums = (int*)p;   p += rad_align(sizeof(int) * (size_t)((n_queries + 1 + 1023) / 1024 + 2));
-    out->stats = (unsigned long long*)p; p += rad_align(16);
-    out->spill = (u64*)p;
-    return true;
+// [grid | counts int32 (nq + 1) | scan scratch | stats u64[2] | spill u64[total]]: the caller-sized tail comes last, so the pieces
+// in front of it (all the count phase needs) lie where they lie whatever the total
+static RadWs rad_ws(WsLayout& L, int64_t n_points, int64_t n_queries, int64_t batch, int64_t total_neighbors) {
+    RadWs o;
+    o.grid = ws_nest(L, grid_ws, n_points, batch);
+    o.counts = L.take<int>((size_t)(n_queries + 2));
+    o.block_sums = L.take<int>((size_t)((n_queries + 1 + 1023) / 1024 + 2));
+    o.stats = L.take<unsigned long long>(2);
+    o.spill = L.take<u64>(0);
+    L.pad(sizeof(u64) * (size_t)total_neighbors);
+    return o;
 }
 
 extern "C" size_t ml3d_radius_workspace_bytes(int64_t n_points, int64_t n_queries, int64_t batch,
                                               int64_t total_neighbors) {
     if (n_points < 0 || n_queries < 0 || batch <= 0 || total_neighbors < 0) return 0;
-    return rad_fixed_bytes(n_points, n_queries, batch) + sizeof(u64) * (size_t)total_neighbors + 256;
+    return ws_bytes_of(rad_ws, n_points, n_queries, batch, total_neighbors) + 256;
 }
 
 static int rad_args(const float* points, const int64_t* prs, const float* queries, const int64_t* qrs,
@@ -401,8 +390,8 @@ extern "C" int ml3d_radius_count(const float* points, const int64_t* points_row_
     int rc = rad_args(points, points_row_splits, queries, queries_row_splits, batch, n_points, n_queries, radius);
     if (rc) return rc;
     if (!out_row_splits || !out_stats) return ML3D_E_INVALID;
-    RadWs W;
-    if (!rad_carve(workspace, workspace_bytes, n_points, n_queries, batch, &W)) return ML3D_E_WORKSPACE;
+    RadWs W;        // (the pieces in front of the tail: all the count phase needs)
+    if (!ws_carve(workspace, workspace_bytes, &W, rad_ws, n_points, n_queries, batch, 0)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Segs ps = {points_row_splits, 0, 0, (int)batch};
     Segs qs = {queries_row_splits, 0, 0, (int)batch};
@@ -439,8 +428,8 @@ extern "C" int ml3d_radius_fill(const float* points, const int64_t* points_row_s
     if (spill ? spill_bytes < sizeof(u64) * (size_t)total_neighbors + 8
               : workspace_bytes < ml3d_radius_workspace_bytes(n_points, n_queries, batch, total_neighbors))
         return ML3D_E_WORKSPACE;
-    RadWs W;
-    if (!rad_carve(workspace, workspace_bytes, n_points, n_queries, batch, &W)) return ML3D_E_WORKSPACE;
+    RadWs W;        // (the pieces in front of the tail; the room for a tail that serves as the spill was checked above)
+    if (!ws_carve(workspace, workspace_bytes, &W, rad_ws, n_points, n_queries, batch, 0)) return ML3D_E_WORKSPACE;
     if (spill) W.spill = (u64*)(((uintptr_t)spill + 7) & ~(uintptr_t)7);
     hipStream_t st = (hipStream_t)stream;
     RadArgs A;
@@ -455,27 +444,22 @@ extern "C" int ml3d_radius_fill(const float* points, const int64_t* points_row_s
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }
 
-static size_t rad_dense_fixed_bytes(int64_t n_points, int64_t n_queries, int64_t batch) {
-    return rad_align(grid_ws_bytes(n_points, batch)) + rad_align(sizeof(int) * (size_t)(n_queries + 2)) + rad_align(16) + 256;
+struct RadDenseWs { GridWs grid; int* counts; unsigned long long* stats; int32_t* stash; };
+
+// [grid | counts | stats | stash int32 [nq][cap]]
+static RadDenseWs rad_dense_ws(WsLayout& L, int64_t n_points, int64_t n_queries, int64_t batch, int cap) {
+    RadDenseWs o;
+    o.grid = ws_nest(L, grid_ws, n_points, batch);
+    o.counts = L.take<int>((size_t)(n_queries + 2));
+    o.stats = L.take<unsigned long long>(2);
+    o.stash = L.take<int32_t>((size_t)n_queries * (size_t)cap);
+    L.pad(256);
+    return o;
 }
 
 extern "C" size_t ml3d_radius_dense_workspace_bytes(int64_t n_points, int64_t n_queries, int64_t batch, int cap) {
     if (n_points < 0 || n_queries < 0 || batch <= 0 || cap <= 0 || cap > RAD_LDS_ROW) return 0;
-    return rad_dense_fixed_bytes(n_points, n_queries, batch) + rad_align(sizeof(int32_t) * (size_t)n_queries * (size_t)cap) + 256;
-}
-
-struct RadDenseWs { GridWs grid; int* counts; unsigned long long* stats; int32_t* stash; };
-
-static bool rad_dense_carve(void* ws, size_t bytes, int64_t n_points, int64_t n_queries, int64_t batch, int cap, RadDenseWs* out) {
-    if (bytes < ml3d_radius_dense_workspace_bytes(n_points, n_queries, batch, cap)) return false;
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    const size_t gb = grid_ws_bytes(n_points, batch);
-    if (!grid_ws_carve(p, gb, n_points, batch, &out->grid)) return false;
-    p += rad_align(gb);
-    out->counts = (int*)p;                  p += rad_align(sizeof(int) * (size_t)(n_queries + 2));
-    out->stats = (unsigned long long*)p;    p += rad_align(16);
-    out->stash = (int32_t*)p;
-    return true;
+    return ws_bytes_of(rad_dense_ws, n_points, n_queries, batch, cap);
 }
 
 extern "C" int ml3d_radius_dense_gather(const float* points, const int64_t* points_row_splits, const float* queries,
@@ -486,7 +470,7 @@ extern "C" int ml3d_radius_dense_gather(const float* points, const int64_t* poin
     if (rc) return rc;
     if (!out_stats || cap <= 0 || cap > RAD_LDS_ROW) return ML3D_E_INVALID;
     RadDenseWs W;
-    if (!rad_dense_carve(workspace, workspace_bytes, n_points, n_queries, batch, cap, &W)) return ML3D_E_WORKSPACE;
+    if (!ws_carve(workspace, workspace_bytes, &W, rad_dense_ws, n_points, n_queries, batch, cap)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Segs ps = {points_row_splits, 0, 0, (int)batch};
     Segs qs = {queries_row_splits, 0, 0, (int)batch};
@@ -511,7 +495,7 @@ extern "C" int ml3d_radius_dense_expand(int64_t n_points, int64_t n_queries, int
     if (n_queries == 0 || dense_cols == 0) return 0;
     if (!out_index) return ML3D_E_INVALID;
     RadDenseWs W;
-    if (!rad_dense_carve(workspace, workspace_bytes, n_points, n_queries, batch, cap, &W)) return ML3D_E_WORKSPACE;
+    if (!ws_carve(workspace, workspace_bytes, &W, rad_dense_ws, n_points, n_queries, batch, cap)) return ML3D_E_WORKSPACE;
     const int64_t total = n_queries * dense_cols;
     const unsigned nb = (unsigned)((total + 255) / 256 < 262144 ? (total + 255) / 256 : 262144);
     hipLaunchKernelGGL(radius_expand, dim3(nb), dim3(256), 0, (hipStream_t)stream, W.stash, W.counts, n_queries, cap, dense_cols,

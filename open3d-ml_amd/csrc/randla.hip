@@ -2871,7 +2871,7 @@ extern "C" int ml3d_randla_forward_ordered(const ml3d_randla_desc* d, const floa
     Layout L;
     make_layout(d, &L);
     auto P = [&](int slot) { return params + L.off[slot]; };
-    float* wsf = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* wsf = (float*)ws_align(workspace);
     auto take = [&](int64_t count) { float* p = wsf; wsf += (count + 63) & ~(int64_t)63; return p; };
 
     // scratch for the bf16 planes of one weight matrix (deep Linears on the bf16 matrix pipe: launch_linear_auto)

@@ -11,6 +11,8 @@
 
 #include <gfx950_ops.h>
 
+#include "workspace.h"
+
 namespace ml3d {
 
 typedef unsigned long long u64;
@@ -23,8 +25,8 @@ struct SortWs {
     int64_t n;
 };
 
-size_t sort_ws_bytes(int64_t n);
-bool sort_ws_carve(void* ws, size_t bytes, int64_t n, SortWs* out);
+// THE layout of the sort's scratch (workspace.h); every user nests it in a workspace of its own: ws_nest(L, sort_ws, n)
+SortWs sort_ws(WsLayout& L, int64_t n);
 // Sorts ascending by the low `key_bits` bits of the key, stable.  The result is left in
 // (keys, vals); an odd number of passes is rounded up so no copy-back is needed.
 // allow_odd: an odd number of passes is NOT rounded up; the result then lies in (ws.keys_alt, ws.vals_alt) -- sort_result_in_alt(n,
@@ -75,8 +77,7 @@ __device__ __forceinline__ uint32_t fs_wait(const uint32_t* p, uint32_t tag) {
 }
 inline int fused_tiles(int64_t n) { return (int)((n + FS_TILE - 1) / FS_TILE); }
 inline bool fused_sort_fits(int64_t n, int key_bits) { return n > 0 && key_bits <= 32 && fused_tiles(n) <= FS_MAX_TILES; }
-size_t fused_ws_bytes(int64_t n, int64_t batch);
-bool fused_ws_carve(void* ws, size_t bytes, int64_t n, int64_t batch, FusedWs* out);
+FusedWs fused_ws(WsLayout& L, int64_t n, int64_t batch);
 // Sorts (a_keys, position) pairs ascending by the low key_bits bits, stable; the first pass takes the POSITION of a key as its value
 // (no value array is read).  ghist must hold the digit histograms (8 bits per pass, pass p at ghist + 256 p).  Returns the
 // number of passes: odd -> the result lies in (b_keys, b_vals), even -> in (a_keys, a_vals).  < 0: launch failure.

@@ -5,31 +5,18 @@
 
 namespace ml3d {
 
-static inline size_t sort_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int64_t sort_blocks(int64_t n) { return (n + 1023) / 1024; }
 
-size_t sort_ws_bytes(int64_t n) {
-    int64_t nb = sort_blocks(n > 0 ? n : 1);
-    int64_t hist = 1 + 256 * nb;
-    size_t b = 0;
-    b += sort_align(sizeof(u64) * (size_t)(n > 0 ? n : 1));
-    b += sort_align(sizeof(uint32_t) * (size_t)(n > 0 ? n : 1));
-    b += sort_align(sizeof(int) * (size_t)hist);
-    b += sort_align(sizeof(int) * (size_t)((hist + 1023) / 1024 + 1));
-    return b + 256;
-}
-
-bool sort_ws_carve(void* ws, size_t bytes, int64_t n, SortWs* out) {
-    if (bytes < sort_ws_bytes(n)) return false;
-    int64_t nb = sort_blocks(n > 0 ? n : 1);
-    int64_t hist = 1 + 256 * nb;
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    out->keys_alt = (u64*)p;       p += sort_align(sizeof(u64) * (size_t)(n > 0 ? n : 1));
-    out->vals_alt = (uint32_t*)p;  p += sort_align(sizeof(uint32_t) * (size_t)(n > 0 ? n : 1));
-    out->hist = (int*)p;           p += sort_align(sizeof(int) * (size_t)hist);
-    out->block_sums = (int*)p;
-    out->n = n;
-    return true;
+SortWs sort_ws(WsLayout& L, int64_t n) {
+    const int64_t m = n > 0 ? n : 1;
+    const int64_t hist = 1 + 256 * sort_blocks(m);
+    SortWs o;
+    o.keys_alt = L.take<u64>((size_t)m);
+    o.vals_alt = L.take<uint32_t>((size_t)m);
+    o.hist = L.take<int>((size_t)hist);
+    o.block_sums = L.take<int>((size_t)((hist + 1023) / 1024 + 1));
+    o.n = n;
+    return o;
 }
 
 // hist[1 + d * nb + blk] = number of keys of block blk whose digit is d  (hist[0] = 0);
@@ -166,42 +153,25 @@ int sort_pairs_u64(u64* keys, uint32_t* vals, int64_t n, int key_bits, const Sor
 }
 
 // ---- fused passes (sort.h) ----------------------------------------------------------------------------------------------------------
-static inline size_t fs_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-size_t fused_ws_bytes(int64_t n, int64_t batch) {
+// (the pieces are ONE run, base .. base + bytes: fused_ws_zero clears them with one fill)
+FusedWs fused_ws(WsLayout& L, int64_t n, int64_t batch) {
     const size_t tiles = (size_t)fused_tiles(n > 0 ? n : 1);
-    size_t b = 0;
-    b += fs_al(4 * 4 * 256);                       // ghist
-    b += fs_al(4 * 8);                             // ticket
-    b += fs_al(4 * 6 * FS_MAX_GROUPS);             // gcnt
-    b += fs_al(4 * tiles * 256);                   // agg
-    b += fs_al(4 * FS_MAX_GROUPS * 256);           // gtot
-    b += fs_al(4 * tiles * 4);                     // tA
-    b += fs_al(4 * FS_MAX_GROUPS * 4);             // gA
-    b += fs_al(4 * tiles * 4);                     // tC
-    b += fs_al(4 * FS_MAX_GROUPS * 4);             // gC
-    b += fs_al(4 * (size_t)(batch + 2));           // fvf
-    return b + 256;
-}
-
-bool fused_ws_carve(void* ws, size_t bytes, int64_t n, int64_t batch, FusedWs* o) {
-    if (bytes < fused_ws_bytes(n, batch)) return false;
-    const size_t tiles = (size_t)fused_tiles(n > 0 ? n : 1);
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    o->base = p;
-    o->ghist = (int*)p;          p += fs_al(4 * 4 * 256);
-    o->ticket = (uint32_t*)p;    p += fs_al(4 * 8);
-    o->gcnt = (uint32_t*)p;      p += fs_al(4 * 6 * FS_MAX_GROUPS);
-    o->agg = (uint32_t*)p;       p += fs_al(4 * tiles * 256);
-    o->gtot = (uint32_t*)p;      p += fs_al(4 * FS_MAX_GROUPS * 256);
-    o->tA = (uint32_t*)p;        p += fs_al(4 * tiles * 4);
-    o->gA = (uint32_t*)p;        p += fs_al(4 * FS_MAX_GROUPS * 4);
-    o->tC = (uint32_t*)p;        p += fs_al(4 * tiles * 4);
-    o->gC = (uint32_t*)p;        p += fs_al(4 * FS_MAX_GROUPS * 4);
-    o->fvf = (uint32_t*)p;       p += fs_al(4 * (size_t)(batch + 2));
-    o->bytes = (size_t)(p - o->base);
-    o->tiles = (int)tiles;
-    return true;
+    const size_t at = L.bytes();
+    FusedWs o;
+    o.ghist = L.take<int>(4 * 256);
+    o.ticket = L.take<uint32_t>(8);
+    o.gcnt = L.take<uint32_t>(6 * FS_MAX_GROUPS);
+    o.agg = L.take<uint32_t>(tiles * 256);
+    o.gtot = L.take<uint32_t>(FS_MAX_GROUPS * 256);
+    o.tA = L.take<uint32_t>(tiles * 4);
+    o.gA = L.take<uint32_t>(FS_MAX_GROUPS * 4);
+    o.tC = L.take<uint32_t>(tiles * 4);
+    o.gC = L.take<uint32_t>(FS_MAX_GROUPS * 4);
+    o.fvf = L.take<uint32_t>((size_t)(batch + 2));
+    o.base = (char*)o.ghist;
+    o.bytes = L.bytes() - at;
+    o.tiles = (int)tiles;
+    return o;
 }
 
 // One pass = one launch.  Tile = 2048 keys in input order; wave w owns the contiguous quarter [512 w, 512 w + 512) and walks it in

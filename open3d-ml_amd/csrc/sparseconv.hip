@@ -167,12 +167,18 @@ __global__ __launch_bounds__(256) void scn_bn_relu_rows(const float* __restrict_
     out[r * ldo + col] = v > 0.f ? v : 0.f;
 }
 
-static inline size_t scn_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static int scn_bits(u64 v) {
-    int bits = 1;
-    while (bits < 64 && (v >> bits) != 0) ++bits;
-    return bits;
+// keys, vals [n]; incl [n] head flags -> inclusive scan; block_sums: scan scratch; ukeys [levels][n] the unique keys of every level
+struct ScnBuildWs { u64* keys; uint32_t* vals; int *incl, *block_sums; u64* ukeys; SortWs sort; };
+static ScnBuildWs scn_build_ws(WsLayout& L, int64_t n, int levels) {
+    ScnBuildWs o;
+    o.keys = L.take<u64>((size_t)n);
+    o.vals = L.take<uint32_t>((size_t)n);
+    o.incl = L.take<int>((size_t)n);
+    o.block_sums = L.take<int>((size_t)((n + 1023) / 1024 + 2));
+    o.ukeys = L.take<u64>((size_t)n * (size_t)levels);
+    o.sort = ws_nest(L, sort_ws, n);
+    L.pad(768);
+    return o;
 }
 
 static inline unsigned scn_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -183,9 +189,7 @@ using namespace ml3d;
 
 extern "C" size_t ml3d_scn_build_workspace_bytes(int64_t n, int levels) {
     if (n <= 0 || levels <= 0 || levels > SCN_MAX_LEVELS) return 0;
-    return scn_align(sizeof(u64) * (size_t)n) + scn_align(sizeof(uint32_t) * (size_t)n) + scn_align(sizeof(int) * (size_t)n) +
-           scn_align(sizeof(int) * (size_t)((n + 1023) / 1024 + 2)) + scn_align(sizeof(u64) * (size_t)n * (size_t)levels) +
-           sort_ws_bytes(n) + 1024;
+    return ws_bytes_of(scn_build_ws, n, levels);
 }
 
 extern "C" int ml3d_scn_build(const float* points, const float* feat, int64_t ldf, int feat_channels, int64_t n,
@@ -199,18 +203,11 @@ extern "C" int ml3d_scn_build(const float* points, const float* feat, int64_t ld
     if (row_splits_host[0] != 0 || row_splits_host[batch] != n) return ML3D_E_INVALID;
     for (int b = 0; b < batch; ++b)
         if (row_splits_host[b + 1] < row_splits_host[b]) return ML3D_E_INVALID;
-    if (!workspace || workspace_bytes < ml3d_scn_build_workspace_bytes(n, levels)) return ML3D_E_WORKSPACE;
-    char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    u64* keys = (u64*)p;             p += scn_align(sizeof(u64) * (size_t)n);
-    uint32_t* vals = (uint32_t*)p;   p += scn_align(sizeof(uint32_t) * (size_t)n);
-    int* incl = (int*)p;             p += scn_align(sizeof(int) * (size_t)n);
-    int* block_sums = (int*)p;       p += scn_align(sizeof(int) * (size_t)((n + 1023) / 1024 + 2));
-    u64* ukeys = (u64*)p;            p += scn_align(sizeof(u64) * (size_t)n * (size_t)levels);
-    SortWs sw;
-    if (!sort_ws_carve(p, sort_ws_bytes(n), n, &sw)) return ML3D_E_WORKSPACE;
+    ScnBuildWs W;
+    if (!workspace || !ws_carve(workspace, workspace_bytes, &W, scn_build_ws, n, levels)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const u64 invalid = (u64)batch << 36;
-    const int key_bits = scn_bits(invalid);
+    const int key_bits = key_bits_for(invalid);
     const unsigned nb = scn_blocks(n);
 
     // rulebook entries nobody writes are -1 (absent child / not this row's parity); rows past a level's count stay -1 as well
@@ -222,30 +219,30 @@ extern "C" int ml3d_scn_build(const float* points, const float* feat, int64_t ld
         const int64_t first = row_splits_host[b], last = row_splits_host[b + 1];
         if (last == first) continue;
         hipLaunchKernelGGL(scn_point_keys, dim3(scn_blocks(last - first)), dim3(256), 0, st, points, first, last, (u64)b, grid_size,
-                           invalid, keys, vals);
+                           invalid, W.keys, W.vals);
     }
     if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
     for (int l = 0; l < levels; ++l) {
-        u64* uk = ukeys + (size_t)l * (size_t)n;
+        u64* uk = W.ukeys + (size_t)l * (size_t)n;
         int32_t* co = coords + (size_t)l * (size_t)n * 4;
         if (l > 0) {
             hipLaunchKernelGGL(scn_parent_keys, dim3(nb), dim3(256), 0, st, (const u64*)(uk - n), (const int32_t*)(counts + l - 1), n,
-                               invalid, keys, vals);
+                               invalid, W.keys, W.vals);
             if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
         }
-        if (sort_pairs_u64(keys, vals, n, key_bits, sw, st, true)) return ML3D_E_LAUNCH;
+        if (sort_pairs_u64(W.keys, W.vals, n, key_bits, W.sort, st, true)) return ML3D_E_LAUNCH;
         const bool alt = sort_result_in_alt(n, key_bits);
-        const u64* sk = alt ? sw.keys_alt : keys;
-        const uint32_t* sv = alt ? sw.vals_alt : vals;
-        hipLaunchKernelGGL(scn_heads, dim3(nb), dim3(256), 0, st, sk, n, invalid, incl);
+        const u64* sk = alt ? W.sort.keys_alt : W.keys;
+        const uint32_t* sv = alt ? W.sort.vals_alt : W.vals;
+        hipLaunchKernelGGL(scn_heads, dim3(nb), dim3(256), 0, st, sk, n, invalid, W.incl);
         if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
-        if (scan_inclusive_i32(incl, n, block_sums, st)) return ML3D_E_LAUNCH;
+        if (scan_inclusive_i32(W.incl, n, W.block_sums, st)) return ML3D_E_LAUNCH;
         if (l == 0) {
-            hipLaunchKernelGGL(scn_level0, dim3(nb), dim3(256), 0, st, sk, sv, (const int*)incl, n, invalid, feat, ldf, feat_channels, uk,
+            hipLaunchKernelGGL(scn_level0, dim3(nb), dim3(256), 0, st, sk, sv, (const int*)W.incl, n, invalid, feat, ldf, feat_channels, uk,
                                co, index_map, feat0, ldo, counts);
         } else {
             const size_t lo = (size_t)(l - 1) * (size_t)n;
-            hipLaunchKernelGGL(scn_level_up, dim3(nb), dim3(256), 0, st, sk, sv, (const int*)incl, n, invalid, (const u64*)(uk - n), uk, co,
+            hipLaunchKernelGGL(scn_level_up, dim3(nb), dim3(256), 0, st, sk, sv, (const int*)W.incl, n, invalid, (const u64*)(uk - n), uk, co,
                                parent + lo, ptap + lo, up8 + lo * 8, child8 + (size_t)l * (size_t)n * 8, counts + l);
         }
         if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;

@@ -770,7 +770,7 @@ extern "C" size_t ml3d_batchnorm_train_workspace_bytes(int channels) {
     return channels > 0 ? sizeof(double) * 2 * (size_t)channels + 256 : 0;
 }
 
-static double* bn_ws(void* workspace) { return (double*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
+static double* bn_ws(void* workspace) { return (double*)ws_align(workspace); }
 
 extern "C" int ml3d_batchnorm_train_forward(const float* x, int64_t rows, int channels, const float* gamma, const float* beta, float eps,
                                             int act, float slope, float* y, float* save_mean, float* save_var, float* save_invstd,
@@ -980,7 +980,7 @@ extern "C" int ml3d_randla_attention_stage_backward(const float* f, const float*
     AttnArgs A = {};
     A.f = f; A.enc = enc; A.idx = neighbor_idx; A.w = weight; A.wt = weight_t; A.bias = bias; A.batch = batch; A.n = n; A.c1 = c1; A.c2 = c2;
     A.out = const_cast<float*>(out); A.gout = grad_out; A.gf = grad_f; A.genc = grad_enc; A.gw = grad_weight; A.gbias = grad_bias;
-    float* partial = (float*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float* partial = (float*)ws_align(workspace);
     int64_t tiles;
     const int groups = attn_bwd_plan(npts, d, &tiles);
     const dim3 grid((unsigned)groups), block(256);

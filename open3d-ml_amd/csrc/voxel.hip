@@ -24,8 +24,6 @@
 
 namespace ml3d {
 
-static inline size_t vx_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // workspace shared by voxelize and subsample
 struct GroupWs {
     u64* keys;          // [n]
@@ -44,49 +42,24 @@ struct GroupWs {
     int batch;
 };
 
-static size_t group_ws_bytes(int64_t n, int64_t batch) {
-    int64_t m = n > 0 ? n : 1;
-    size_t b = 0;
-    b += vx_align(sizeof(u64) * (size_t)m);
-    b += vx_align(sizeof(uint32_t) * (size_t)m);
-    b += 3 * vx_align(sizeof(int) * (size_t)(m + 2));
-    b += vx_align(sizeof(int) * (size_t)(batch + 2));
-    b += vx_align(sizeof(int) * (size_t)((m + 1 + 1023) / 1024 + 2));
-    b += vx_align(sizeof(unsigned) * 6 * (size_t)batch);
-    b += vx_align(sizeof(unsigned) * GRID_LEVELS * (size_t)batch);
-    b += vx_align(sizeof(float) * 8 * (size_t)batch);
-    b += vx_align(sort_ws_bytes(m));
-    b += fused_ws_bytes(m, batch);
-    return b + 256;
-}
-
-static bool group_ws_carve(void* ws, size_t bytes, int64_t n, int64_t batch, GroupWs* o) {
-    if (bytes < group_ws_bytes(n, batch)) return false;
-    int64_t m = n > 0 ? n : 1;
-    char* p = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    o->keys = (u64*)p;          p += vx_align(sizeof(u64) * (size_t)m);
-    o->vals = (uint32_t*)p;     p += vx_align(sizeof(uint32_t) * (size_t)m);
-    o->flags = (int*)p;         p += vx_align(sizeof(int) * (size_t)(m + 2));
-    o->hp = (int*)p;            p += vx_align(sizeof(int) * (size_t)(m + 2));
-    o->cnt = (int*)p;           p += vx_align(sizeof(int) * (size_t)(m + 2));
-    o->fv = (int*)p;            p += vx_align(sizeof(int) * (size_t)(batch + 2));
-    o->block_sums = (int*)p;    p += vx_align(sizeof(int) * (size_t)((m + 1 + 1023) / 1024 + 2));
-    o->bbox = (unsigned*)p;     p += vx_align(sizeof(unsigned) * 6 * (size_t)batch);
-    o->occ = (unsigned*)p;      p += vx_align(sizeof(unsigned) * GRID_LEVELS * (size_t)batch);
-    o->seg = (float*)p;         p += vx_align(sizeof(float) * 8 * (size_t)batch);
-    size_t sb = sort_ws_bytes(m);
-    if (!sort_ws_carve(p, sb, m, &o->sort)) return false;
-    p += vx_align(sb);
-    if (!fused_ws_carve(p, fused_ws_bytes(m, batch), m, batch, &o->fused)) return false;
-    o->n = n;
-    o->batch = (int)batch;
-    return true;
-}
-
-static int bits_for(unsigned long long v) {   // bits needed to represent every value in [0, v]
-    int b = 1;
-    while (b < 64 && (v >> b) != 0ull) ++b;
-    return b;
+static GroupWs group_ws(WsLayout& L, int64_t n, int64_t batch) {
+    const int64_t m = n > 0 ? n : 1;
+    GroupWs o;
+    o.keys = L.take<u64>((size_t)m);
+    o.vals = L.take<uint32_t>((size_t)m);
+    o.flags = L.take<int>((size_t)(m + 2));
+    o.hp = L.take<int>((size_t)(m + 2));
+    o.cnt = L.take<int>((size_t)(m + 2));
+    o.fv = L.take<int>((size_t)(batch + 2));
+    o.block_sums = L.take<int>((size_t)((m + 1 + 1023) / 1024 + 2));
+    o.bbox = L.take<unsigned>(6 * (size_t)batch);
+    o.occ = L.take<unsigned>(GRID_LEVELS * (size_t)batch);
+    o.seg = L.take<float>(8 * (size_t)batch);
+    o.sort = ws_nest(L, sort_ws, m);
+    o.fused = ws_nest(L, fused_ws, m, batch);
+    o.n = n;
+    o.batch = (int)batch;
+    return o;
 }
 
 // ---- shared grouping kernels -----------------------------------------------------------------------
@@ -885,7 +858,7 @@ static int vox_params(const float* vs, const float* rmin, const float* rmax, int
 static bool vox_fused(int64_t n, int64_t batch, const VoxParams& P) {
     static const bool off = [] { const char* e = getenv("ML3D_VOX_FUSED"); return e && atoi(e) == 0; }();
     const double inval = (double)batch * (double)P.cells;
-    return !off && inval <= 4294967295.0 && fused_sort_fits(n, bits_for((u64)batch * (u64)P.cells));
+    return !off && inval <= 4294967295.0 && fused_sort_fits(n, key_bits_for((u64)batch * (u64)P.cells));
 }
 
 struct VoxFusedBufs { uint32_t *ka, *va, *kb, *vb; };
@@ -899,7 +872,7 @@ using namespace ml3d;
 
 extern "C" size_t ml3d_voxelize_workspace_bytes(int64_t n_points, int64_t batch) {
     if (n_points < 0 || batch <= 0) return 0;
-    return group_ws_bytes(n_points, batch);
+    return ws_bytes_of(group_ws, n_points, batch);
 }
 
 extern "C" int ml3d_voxelize_count(const float* points, int64_t point_stride, const int64_t* row_splits, int64_t batch,
@@ -914,7 +887,7 @@ extern "C" int ml3d_voxelize_count(const float* points, int64_t point_stride, co
     int rc = vox_params(voxel_size_host, range_min_host, range_max_host, max_points_per_voxel, max_voxels, batch, &P);
     if (rc) return rc;
     GroupWs W;
-    if (!group_ws_carve(workspace, workspace_bytes, n_points, batch, &W)) return ML3D_E_WORKSPACE;
+    if (!ws_carve(workspace, workspace_bytes, &W, group_ws, n_points, batch)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Segs S = {row_splits, 0, 0, (int)batch};
     const int64_t n = n_points;
@@ -923,7 +896,7 @@ extern "C" int ml3d_voxelize_count(const float* points, int64_t point_stride, co
     if (vox_fused(n, batch, P)) {
         const FusedWs& F = W.fused;
         const VoxFusedBufs B = vox_fused_bufs(W);
-        const int bits = bits_for(inval), passes = fused_passes(bits);
+        const int bits = key_bits_for(inval), passes = fused_passes(bits);
         zero_async(F.base, F.bytes, st);
         const unsigned kb = nb < 512u ? nb : 512u;
         hipLaunchKernelGGL(vox_keys32, dim3(kb), dim3(256), 0, st, points, point_stride, S, n, P, (uint32_t)inval, passes, B.ka, F.ghist);
@@ -944,7 +917,7 @@ extern "C" int ml3d_voxelize_count(const float* points, int64_t point_stride, co
         hipLaunchKernelGGL(vox_keys, dim3(nb), dim3(256), 0, st, points, point_stride, S, n, P, W.keys, W.vals);
         VX_CHECK();
     }
-    rc = group_pairs(W, n, bits_for(inval), inval, (u64)P.cells, -1, st);
+    rc = group_pairs(W, n, key_bits_for(inval), inval, (u64)P.cells, -1, st);
     if (rc) return rc;
     if (n > 0) {
         hipLaunchKernelGGL(vox_counts, dim3(nb), dim3(256), 0, st, W.keys, W.flags, n, W.hp, W.fv, P, W.cnt);
@@ -967,7 +940,7 @@ extern "C" int ml3d_voxelize_fill(int64_t batch, int64_t n_points, const float* 
     int rc = vox_params(voxel_size_host, range_min_host, range_max_host, max_points_per_voxel, max_voxels, batch, &P);
     if (rc) return rc;
     GroupWs W;
-    if (!group_ws_carve(workspace, workspace_bytes, n_points, batch, &W)) return ML3D_E_WORKSPACE;
+    if (!ws_carve(workspace, workspace_bytes, &W, group_ws, n_points, batch)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     if (n_points == 0) {
         (void)hipMemsetAsync(out_point_row_splits, 0, sizeof(int64_t), st);
@@ -975,14 +948,14 @@ extern "C" int ml3d_voxelize_fill(int64_t batch, int64_t n_points, const float* 
     }
     if (vox_fused(n_points, batch, P)) {
         const VoxFusedBufs B = vox_fused_bufs(W);
-        const bool in_b = fused_passes(bits_for((u64)batch * (u64)P.cells)) & 1;
+        const bool in_b = fused_passes(key_bits_for((u64)batch * (u64)P.cells)) & 1;
         hipLaunchKernelGGL(vox_fill32, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, st, in_b ? B.kb : B.ka, in_b ? B.vb : B.va,
                            n_points, W.hp, W.fv, W.cnt, batch_splits, P, (int)batch, out_voxel_coords, out_point_indices,
                            out_point_row_splits);
         VX_CHECK();
         return 0;
     }
-    group_swap_if_alt(W, n_points, bits_for((u64)batch * (u64)P.cells));
+    group_swap_if_alt(W, n_points, key_bits_for((u64)batch * (u64)P.cells));
     hipLaunchKernelGGL(vox_fill, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, st, W.keys, W.vals, W.flags,
                        n_points, W.hp, W.fv, W.cnt, batch_splits, P, out_voxel_coords, out_point_indices,
                        out_point_row_splits);
@@ -992,7 +965,7 @@ extern "C" int ml3d_voxelize_fill(int64_t batch, int64_t n_points, const float* 
 
 extern "C" size_t ml3d_subsample_workspace_bytes(int64_t n_points, int64_t batch) {
     if (n_points < 0 || batch <= 0) return 0;
-    return group_ws_bytes(n_points, batch);
+    return ws_bytes_of(group_ws, n_points, batch);
 }
 
 extern "C" int ml3d_subsample_count(const float* points, const int64_t* row_splits, int64_t batch, int64_t n_points,
@@ -1002,7 +975,7 @@ extern "C" int ml3d_subsample_count(const float* points, const int64_t* row_spli
         !out_lengths || !out_stats || (n_points > 0 && !points))
         return ML3D_E_INVALID;
     GroupWs W;
-    if (!group_ws_carve(workspace, workspace_bytes, n_points, batch, &W)) return ML3D_E_WORKSPACE;
+    if (!ws_carve(workspace, workspace_bytes, &W, group_ws, n_points, batch)) return ML3D_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     Segs S = {row_splits, 0, 0, (int)batch};
     const int64_t n = n_points;
@@ -1016,7 +989,7 @@ extern "C" int ml3d_subsample_count(const float* points, const int64_t* row_spli
                            W.keys, W.vals);
         VX_CHECK();
     }
-    int rc = group_pairs(W, n, SUB_ITEM_SHIFT + bits_for((u64)batch), ~0ull, 0ull, SUB_ITEM_SHIFT, st);
+    int rc = group_pairs(W, n, SUB_ITEM_SHIFT + key_bits_for((u64)batch), ~0ull, 0ull, SUB_ITEM_SHIFT, st);
     if (rc) return rc;
     hipLaunchKernelGGL(sub_lengths, dim3((unsigned)(batch + 63) / 64), dim3(64), 0, st, W.fv, (int)batch, out_lengths,
                        out_stats);
@@ -1032,8 +1005,8 @@ extern "C" int ml3d_subsample_fill(const float* points, const float* features, i
     if (n_points == 0) return 0;
     if (!points || !out_points) return ML3D_E_INVALID;
     GroupWs W;
-    if (!group_ws_carve(workspace, workspace_bytes, n_points, batch, &W)) return ML3D_E_WORKSPACE;
-    group_swap_if_alt(W, n_points, SUB_ITEM_SHIFT + bits_for((u64)batch));
+    if (!ws_carve(workspace, workspace_bytes, &W, group_ws, n_points, batch)) return ML3D_E_WORKSPACE;
+    group_swap_if_alt(W, n_points, SUB_ITEM_SHIFT + key_bits_for((u64)batch));
     hipLaunchKernelGGL(sub_fill, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W.vals,
                        W.flags, n_points, W.hp, points, features, feature_dim, labels, out_points, out_features,
                        out_labels);
