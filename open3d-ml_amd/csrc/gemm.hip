@@ -1139,7 +1139,7 @@ static int pick_splits(int64_t M, int N, int K) {
     // (K in [512, 768) -- RandLA's decoder and 512-wide Linears -- keeps round 1's numbers: measured 0.4 % faster there)
     const int64_t thr = K >= 768 ? 1024 : 256;
     const int64_t aim = K >= 768 ? 1024 : 512;
-    if (tiles >= thr || K < 512) return 1;
+    if (tiles >= thr || K < 512 || tiles <= 0) return 1;    // (tiles == 0: an empty problem, sized before it is refused)
     int64_t want = (aim + tiles - 1) / tiles;
     int64_t maxs = K / 128;                              // at least 4 chunks per split
     int64_t s = want < maxs ? want : maxs;

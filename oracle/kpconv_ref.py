@@ -160,13 +160,21 @@ def _unary(sd, prefix, x, cfg, use_bn=True, relu=True):
     return F.leaky_relu(x, cfg.get("l_relu", 0.1)) if relu else x
 
 
-def kpconv_rigid(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent):
-    """KPConv.forward, non-deformable, KP_influence='linear', aggregation 'sum' (kpconv.py:1048-1159)."""
+def kpconv_rigid(q_pts, s_pts, neighb_inds, x, kernel_points, weights, extent, influence="linear"):
+    """KPConv.forward, non-deformable, aggregation 'sum' (kpconv.py:1048-1159); ``influence`` = KP_influence: "constant" |
+    "linear" | "gaussian" (kpconv.py:1105-1125, radius_gaussian with sigma = 0.3 extent)."""
     s_pad = torch.cat((s_pts, torch.zeros_like(s_pts[:1, :]) + 1e6), 0)
     neighbors = s_pad[neighb_inds, :] - q_pts.unsqueeze(1)
     differences = neighbors.unsqueeze(2) - kernel_points
     sq = torch.sum(differences ** 2, dim=3)
-    w = torch.clamp(1 - torch.sqrt(sq) / extent, min=0.0).transpose(1, 2)
+    if influence == "constant":
+        w = torch.ones_like(sq).transpose(1, 2)
+    elif influence == "linear":
+        w = torch.clamp(1 - torch.sqrt(sq) / extent, min=0.0).transpose(1, 2)
+    elif influence == "gaussian":
+        w = torch.exp(-sq / (2 * (extent * 0.3) ** 2 + 1e-9)).transpose(1, 2)
+    else:
+        raise ValueError("KP_influence must be 'constant', 'linear' or 'gaussian'")
     xp = torch.cat((x, torch.zeros_like(x[:1, :])), 0)
     nx = xp[neighb_inds]
     wf = torch.matmul(w, nx).permute(1, 0, 2)
@@ -210,7 +218,8 @@ def _conv(sd, p, b, q_pts, s_pts, inds, x, cfg):
     if "deform" in b["name"]:
         return kpconv_deformable(q_pts, s_pts, inds, x, sd[p + ".kernel_points"], sd[p + ".weights"], b["extent"],
                                  sd[p + ".offset_conv.weights"], sd[p + ".offset_bias"], cfg.get("modulated", False))
-    return kpconv_rigid(q_pts, s_pts, inds, x, sd[p + ".kernel_points"], sd[p + ".weights"], b["extent"])
+    return kpconv_rigid(q_pts, s_pts, inds, x, sd[p + ".kernel_points"], sd[p + ".weights"], b["extent"],
+                        cfg.get("KP_influence", "linear"))
 
 
 def max_pool(x, inds):

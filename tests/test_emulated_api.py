@@ -470,7 +470,7 @@ def test_kpconv_autograd_function_matches_torch_autograd_of_the_oracle():
     through the oracle's pure-torch KPConv (oracle/kpconv_ref.kpconv_rigid = kpconv.py:1005-1159): output, d/dx and d/dW, for the
     MFMA aggregation (cin 32), the generic one (cin 8), the first-layer one (cin 4), 96 channels (two lane chunks in the adjoint),
     strided queries and shadow columns anywhere."""
-    _run(r'''
+    out = _run(r'''
 import synth_data
 from oracle import kpconv_ref as K
 from ml3d import ops
@@ -486,10 +486,7 @@ for cin, cout, strided, infl in ((32, 16, False, 1), (8, 24, True, 1), (4, 32, F
     w = torch.from_numpy((rng.standard_normal((15, cin, cout)) * 0.2).astype(np.float32)).requires_grad_(True)
     g = torch.from_numpy(rng.standard_normal((len(qq), cout)).astype(np.float32))
     tq, ts, ti, tk = torch.from_numpy(qq), torch.from_numpy(s), torch.from_numpy(inds), torch.from_numpy(kp)
-    ref = K.kpconv_rigid(tq, ts, ti.long(), x, tk, w, 0.24, influence={1: "linear", 2: "gaussian"}[infl]) if "influence" in K.kpconv_rigid.__code__.co_varnames \
-        else K.kpconv_rigid(tq, ts, ti.long(), x, tk, w, 0.24)
-    if infl != 1 and "influence" not in K.kpconv_rigid.__code__.co_varnames:
-        continue
+    ref = K.kpconv_rigid(tq, ts, ti.long(), x, tk, w, 0.24, influence={1: "linear", 2: "gaussian"}[infl])
     ref.backward(g)
     gx_ref, gw_ref = x.grad.clone(), w.grad.clone()
     x.grad = None; w.grad = None
@@ -499,8 +496,11 @@ for cin, cout, strided, infl in ((32, 16, False, 1), (8, 24, True, 1), (4, 32, F
     assert (out - ref).abs().max() <= 1e-4 * sc(ref), (cin, float((out - ref).abs().max()))
     assert (x.grad - gx_ref).abs().max() <= 1e-4 * sc(gx_ref), (cin, float((x.grad - gx_ref).abs().max()))
     assert (w.grad - gw_ref).abs().max() <= 1e-4 * sc(gw_ref), (cin, float((w.grad - gw_ref).abs().max()))
+    print("case cin=%d influence=%d out=%.3g dx=%.3g dw=%.3g" % (cin, infl, float((out - ref).abs().max()),
+          float((x.grad - gx_ref).abs().max()), float((w.grad - gw_ref).abs().max())))
 print("ok")
 ''')
+    assert out.count("case cin=") == 4 and "case cin=4 influence=2" in out, out      # every case ran, the Gaussian one among them
 
 
 def test_attentive_pool_and_gather_max_functions_match_torch_autograd():

@@ -89,7 +89,7 @@ def test_forward_accepts_the_reference_cpu_int64_batch():
 
 
 def test_other_config_shapes_in_features_5_no_reduce_fc_gaussian():
-    cfg = dict(CFG, in_features_dim=5, reduce_fc=False, first_features_dim=64, KP_extent=1.2, l_relu=0.1,
+    cfg = dict(CFG, in_features_dim=5, reduce_fc=False, first_features_dim=64, KP_extent=1.2, l_relu=0.1, KP_influence="gaussian",
                architecture=["simple", "resnetb", "resnetb_strided", "resnetb", "resnetb_strided", "resnetb",
                              "nearest_upsample", "unary", "nearest_upsample", "unary"], num_layers=3)
     from ml3d.torch.models.kpconv import KPFCNN, KPConvBatch
