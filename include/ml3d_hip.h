@@ -1246,6 +1246,59 @@ int ml3d_pn2_group_rows(const float* y, int64_t ldy, const float* points, const 
 int ml3d_pn2_interpolate(const float* known, int64_t ldk, int64_t batch, int64_t m_known, const int32_t* idx,
                          const float* dist2, const float* weight, int64_t n, int c, float* out, int64_t ldo, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* PointRCNN stage 1 (added at ABI 13: new symbols only, no signature         */
+/*   changed) -- everything between the backbone's features and the region    */
+/*   proposals of the reference's ml3d/torch/models/point_rcnn.py             */
+/*   (mode="RPN").  Kernel launches only, nothing is read back.               */
+/* ------------------------------------------------------------------------- */
+/* ml3d_bin_decode restates decode_bbox_target (point_rcnn.py:1153-1272) with rotate_pc_along_y_torch (:1275-1295).             */
+/*   roi f32 [n, roi_width], roi_width 3 (x, y, z) or 7 (x, y, z, h, w, l, ry); pred_reg f32 rows [n] of stride ld_reg with     */
+/*   `channels` columns (a column slice of a wider buffer works); anchor_size_host f32 [3] is a HOST array; out_boxes f32       */
+/*   [n, 7] = (x, y, z, h, w, l, ry).  With L = int(loc_scope / loc_bin_size) * 2, Y = int(loc_y_scope / loc_y_bin_size) * 2    */
+/*   and H = num_head_bin the columns are  x bins [L] | z bins [L] | (get_xz_fine: x residuals [L] | z residuals [L]) |         */
+/*   (get_y_by_bin: y bins [Y] | y residuals [Y]; else: y offset [1]) | heading bins [H] | heading residuals [H] | size [3];    */
+/*   `channels` must equal that count, ML3D_E_INVALID otherwise.  Every argmax gives a tie to the LOWEST bin (torch.argmax);    */
+/*   inputs are taken to be NaN-free.  float32, one rounding per operation, in the reference's order:                          */
+/*     x = (bin * loc_bin_size + loc_bin_size / 2 - loc_scope) [+ residual * loc_bin_size]            (z alike)                 */
+/*     y = roi_y + offset            or  (bin * loc_y_bin_size + loc_y_bin_size / 2 - loc_y_scope + residual * loc_y_bin_size)  */
+/*                                        + roi_y                                                                               */
+/*     ry = (bin * (2 pi / H) + residual * (pi / H)) % (2 pi),  then  ry -= 2 pi  where ry > pi        (get_ry_fine = 0)         */
+/*     ry = (bin * a + a / 2) + residual * (a / 2) - pi / 4,  a = (pi / 2) / H                        (get_ry_fine = 1)         */
+/*     (h, w, l) = size * anchor + anchor                                                                                       */
+/*   roi_width 7: (x, z) is rotated by -roi_ry (x' = x cos - z sin, z' = x sin + z cos of the angle -roi_ry) and ry += roi_ry;   */
+/*   then x += roi_x, z += roi_z.  A group of 16 lanes per row, coalesced reads, no atomics.                                    */
+int ml3d_bin_decode(const float* roi, int roi_width, const float* pred_reg, int64_t ld_reg, int channels, int64_t n,
+                    const float* anchor_size_host, float loc_scope, float loc_bin_size, int num_head_bin, float loc_y_scope,
+                    float loc_y_bin_size, int get_xz_fine, int get_y_by_bin, int get_ry_fine, float* out_boxes, void* stream);
+
+/* ml3d_rpn_proposals restates ProposalLayer.forward with post_process=True and distance_based_proposal                         */
+/*   (point_rcnn.py:1020-1150) for the whole batch.  scores f32 [batch, n]; boxes f32 [batch, n, 7] as ml3d_bin_decode wrote     */
+/*   them (NOT modified).  Outputs, padding included, are written by the call: out_rois f32 [batch, nms_post, 7] (zero rows    */
+/*   behind the last proposal), out_roi_scores f32 [batch, nms_post] (zeros), out_roi_index int32 [batch, nms_post]: the        */
+/*   item-local source point of each roi, -1 in the padding (an addition to the reference's two outputs).  Per item:           */
+/*     - order: descending score, equal scores by ascending point index (-0.0 == +0.0);                                         */
+/*     - zones on z = boxes[.., 2]: near 0 < z <= 40, far 40 < z <= 80, anything else (NaN too) in no zone;                     */
+/*     - candidates: the first pre_near = int(nms_pre * 0.7) near rows and the first pre_far = nms_pre - pre_near far rows in   */
+/*       that order; an EMPTY far zone takes the near zone's rows [pre_near, pre_near + pre_far) instead;                       */
+/*     - BEV box of a candidate: xywhr_to_xyxyr of columns [0, 2, 3, 5, 6] = (x, z, h, l, ry), exactly as the reference         */
+/*       indexes them: (x - h / 2, z - l / 2, x + h / 2, z + l / 2, ry);                                                        */
+/*     - NMS: ml3d_nms's contract (greedy in the order above, suppressed when IoU > nms_thres), called once per (item, zone);   */
+/*     - kept: the first int(nms_post * 0.7) near survivors, then the first nms_post - int(nms_post * 0.7) far survivors;       */
+/*     - an output row is the box with y + h / 2 (one float32 add: the reference's `proposals[..., 1] += proposals[..., 3] / 2`) */
+/*       and every other column bit for bit.                                                                                    */
+/*   The ONE deviation: the reference asserts when the near zone is empty; here an empty near zone contributes no rows (and an  */
+/*   empty far zone then falls back to nothing).                                                                                */
+/*   Scratch is caller-owned, typed, uninitialised (T = batch * n, P = batch * nms_pre):                                        */
+/*     sort_keys u64 [2 T], sort_vals u32 [2 T], sort_hist int32 [257 * ceil(T / 1024) + 4], lists int32 [2 P + 2 batch],       */
+/*     nms_boxes f32 [6 P], nms_keep int64 [P + 2 batch], nms_workspace of ml3d_nms_workspace_bytes(nms_pre) bytes.             */
+/*   Limits: nms_pre <= 65536, batch <= 65536, T < 2^31 (ML3D_E_UNSUPPORTED).  Launches: 1 + the batch's sort + 1 + the NMS     */
+/*   calls + 1.                                                                                                                  */
+int ml3d_rpn_proposals(const float* scores, const float* boxes, int64_t batch, int64_t n, int64_t nms_pre, int64_t nms_post,
+                       float nms_thres, float* out_rois, float* out_roi_scores, int32_t* out_roi_index, uint64_t* sort_keys,
+                       uint32_t* sort_vals, int32_t* sort_hist, int32_t* lists, float* nms_boxes, int64_t* nms_keep,
+                       void* nms_workspace, size_t nms_workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
