@@ -1299,6 +1299,40 @@ int ml3d_rpn_proposals(const float* scores, const float* boxes, int64_t batch, i
                        uint32_t* sort_vals, int32_t* sort_hist, int32_t* lists, float* nms_boxes, int64_t* nms_keep,
                        void* nms_workspace, size_t nms_workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------- */
+/* PointRCNN stage 2, the pooling (added at ABI 13: a new symbol only).  The  */
+/*   RCNN network behind it runs on entries that exist: ml3d_linear, the FPS, */
+/*   ml3d_ball_query, ml3d_pn2_sa_mlp_max, ml3d_bin_decode, ml3d_nms.         */
+/* ------------------------------------------------------------------------- */
+/* ml3d_roi_pool produces what RCNN.forward reads as pts_input (point_rcnn.py:848-887) in one launch: roipool3d_gpu            */
+/*   (roipool3d_utils.py:24: enlarge_box3d + the open3d wheel's roi_pool), the two extra per-point features and the canonical   */
+/*   transform.  xyz f32 [batch, n, 3]; feat f32 rows [batch * n] of stride ld_feat (`channels` columns); scores f32            */
+/*   [batch, n] (the raw RPN cls); rois f32 [batch, m, 7] = (x, y, z, h, w, l, ry), y the centre of the bottom face.            */
+/*   CONTRACT (UNPINNED against the open3d wheel: the op lives in the wheel, which is not available to this project; the      */
+/*   semantics below are those of the PointRCNN roipool3d kernel the wheel's op was taken from, stated operation by operation; */
+/*   float32, no fused multiply-add):                                                                                           */
+/*     enlarged box: h, w, l each + (2 * extra_width), y + extra_width (one add each); x, z, ry as given                        */
+/*     cy = y - h / 2;  dx = px - x, dy = py - cy, dz = pz - z                                                                  */
+/*     rejected when |dx| > 10 or |dy| > h / 2 or |dz| > 10          (the wheel's 10 m prefilter; it cuts boxes longer than 20 m) */
+/*     xr = dx * cos(ry) + dz * (-sin(ry)),  zr = dx * sin(ry) + dz * cos(ry)                                                   */
+/*     inside  iff  -l / 2 <= xr <= l / 2  and  -w / 2 <= zr <= w / 2                                  (every face closed)       */
+/*     out_pool_idx int32 [batch, m, num_points], item-local: the first num_points inside points in ASCENDING point index;      */
+/*     with 0 < cnt < num_points slot k >= cnt repeats slot k % cnt; with cnt == 0 every slot is -1 and out_empty[b, roi] = 1   */
+/*     (int32 [batch, m], 0 otherwise).  A NaN coordinate is outside.                                                           */
+/*   out_pts_input f32 [batch * m, num_points, 5 + channels], per slot with p = xyz[b, idx] and d = p - (x, y, z) of the roi    */
+/*   AS GIVEN (not enlarged):                                                                                                   */
+/*     [0..2] = (d.x cos(ry) - d.z sin(ry),  d.y,  d.x sin(ry) + d.z cos(ry))                  (rotate_pc_along_y_torch, :1275)  */
+/*     [3]    = 1 / (1 + exp(-scores[b, idx])) > score_thres ? 1 : 0                                                            */
+/*     [4]    = sqrt((p.x p.x + p.y p.y) + p.z p.z) / 70 - 0.5                                                                  */
+/*     [5..]  = feat[b * n + idx, :channels]                                                          (bit for bit)             */
+/*   an empty roi: p = 0 and zeros in [3..] -- the reference subtracts the centre from the wheel's zero rows too.  All-zero     */
+/*   padding rois are pooled like any other.  Every output element is written by the call; nothing is read back; no scratch,    */
+/*   no atomics: one workgroup per (item, roi) ranks the hits by ballot / popcount and stops its walk at num_points hits.      */
+/*   num_points < 1, ld_feat < channels: ML3D_E_INVALID.  batch * n, batch * m * num_points < 2^31 (ML3D_E_UNSUPPORTED).        */
+int ml3d_roi_pool(const float* xyz, const float* feat, int64_t ld_feat, int channels, const float* scores, const float* rois,
+                  int64_t batch, int64_t n, int64_t m, int num_points, float score_thres, float extra_width,
+                  float* out_pts_input, int32_t* out_pool_idx, int32_t* out_empty, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@
 //   ml3d_nms      the existing rotated-BEV NMS, once per (item, zone), on scores that restate the walk order
 //   rpn_collect   one workgroup per item: the first int(0.7 nms_post) near and nms_post - int(0.7 nms_post) far survivors,
 //                 near rows first; y += h / 2; zero / -1 padding.
+//
+// ml3d_roi_pool produces the rows RCNN.forward reads as pts_input (:848-887) in one launch: the open3d wheel's roi_pool on the
+// enlarged boxes, the two extra per-point columns and the canonical transform, without the [B, N, 2 + C] concat.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -256,6 +259,81 @@ rpn_collect(const float* __restrict__ scores, const float* __restrict__ boxes, i
     }
 }
 
+// ---- RoI pooling (stage 2's input) ----------------------------------------------------------------------------------------------------
+// One workgroup per (item, roi), the box in uniform registers.  Phase 1 walks the item's points 256 at a time: a point's slot is
+// the running count + the hits of the waves before + the hits of the lanes below (ballot / popcount, as rpn_zones ranks its zones),
+// so the list comes out in ascending point index without an atomic; the walk ends once S hits are known.  The list lives in the
+// output pool_idx itself.  Phase 2: a wave per output row; slot k reads the hit k % cnt (the wheel's wrap), every lane forms the
+// five leading columns (uniform work), lanes copy the feature row with consecutive addresses on both sides.
+struct RoiPoolArgs {
+    int64_t n, m, ld_feat;
+    int c, s;
+    float score_thres, extra_width;
+};
+
+__global__ void __launch_bounds__(256)
+roi_pool_rows(const float* __restrict__ xyz, const float* __restrict__ feat, const float* __restrict__ scores,
+              const float* __restrict__ rois, RoiPoolArgs A, float* __restrict__ out, int32_t* pool_idx, int32_t* __restrict__ empty) {
+    __shared__ int wsum[4];
+    const int64_t r = blockIdx.x;                             // b * m + roi
+    const int64_t b = r / A.m;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const float* q = rois + r * 7;
+    const float x = q[0], y = q[1], z = q[2], ry = q[6];
+    // enlarge_box3d: one float32 add each
+    const float wide = 2.0f * A.extra_width;
+    const float h = q[3] + wide, w = q[4] + wide, l = q[5] + wide, ye = y + A.extra_width;
+    const float hh = h / 2.0f, hw = w / 2.0f, hl = l / 2.0f;
+    const float cy = ye - hh;
+    const float ca = cosf(ry), sa = sinf(ry);
+    const float* pts = xyz + b * A.n * 3;
+    int32_t* list = pool_idx + r * A.s;
+    int cnt = 0;                                              // hits so far (uniform)
+    for (int64_t p0 = 0; p0 < A.n && cnt < A.s; p0 += 256) {
+        const int64_t p = p0 + t;
+        bool in = false;
+        if (p < A.n) {
+            const float dx = pts[3 * p] - x, dy = pts[3 * p + 1] - cy, dz = pts[3 * p + 2] - z;
+            if (!(fabsf(dx) > 10.0f || fabsf(dy) > hh || fabsf(dz) > 10.0f)) {
+                const float xr = dx * ca + dz * (-sa);
+                const float zr = dx * sa + dz * ca;
+                in = xr >= -hl && xr <= hl && zr >= -hw && zr <= hw;
+            }
+        }
+        const u64 mask = __ballot(in);
+        if (lane == 0) wsum[wv] = __popcll(mask);
+        __syncthreads();
+        int rank = cnt;
+        for (int k = 0; k < wv; ++k) rank += wsum[k];
+        rank += __popcll(mask & ((1ull << lane) - 1ull));
+        if (in && rank < A.s) list[rank] = (int32_t)p;
+        cnt += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();                                      // (also: the list entries are visible to the whole workgroup)
+    }
+    if (cnt > A.s) cnt = A.s;
+    if (t == 0) empty[r] = cnt == 0 ? 1 : 0;
+    const int width = 5 + A.c;
+    for (int k = wv; k < A.s; k += 4) {
+        float* o = out + (r * A.s + k) * width;
+        float px = 0.f, py = 0.f, pz = 0.f, seg = 0.f, depth = 0.f;
+        int64_t src = -1;
+        if (cnt > 0) {
+            src = list[k % cnt];                              // slots below cnt are never written in this phase
+            px = pts[3 * src]; py = pts[3 * src + 1]; pz = pts[3 * src + 2];
+            const float sc = scores[b * A.n + src];
+            seg = 1.0f / (1.0f + expf(-sc)) > A.score_thres ? 1.0f : 0.f;
+            depth = sqrtf((px * px + py * py) + pz * pz) / 70.0f - 0.5f;
+        }
+        if (lane == 0 && k >= cnt) list[k] = (int32_t)src;
+        // the canonical transform, on the roi as given (not the enlarged box)
+        const float dx = px - x, dy = py - y, dz = pz - z;
+        const float xc = dx * ca - dz * sa, zc = dx * sa + dz * ca;
+        const float lead = lane == 0 ? xc : lane == 1 ? dy : lane == 2 ? zc : lane == 3 ? seg : depth;
+        const float* f = feat + (b * A.n + (src < 0 ? 0 : src)) * A.ld_feat;
+        for (int c = lane; c < width; c += 64) o[c] = c < 5 ? lead : (src < 0 ? 0.f : f[c - 5]);
+    }
+}
+
 }  // namespace ml3d
 
 using namespace ml3d;
@@ -348,5 +426,20 @@ extern "C" int ml3d_rpn_proposals(const float* scores, const float* boxes, int64
         hipLaunchKernelGGL(rpn_collect, dim3((unsigned)batch), dim3(256), 0, st, scores, boxes, n, pre, pre_near, 0, 0, (int)nms_post,
                            post_near, cand, counts, nms_keep, kept, out_rois, out_roi_scores, out_roi_index);
     }
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" int ml3d_roi_pool(const float* xyz, const float* feat, int64_t ld_feat, int channels, const float* scores,
+                             const float* rois, int64_t batch, int64_t n, int64_t m, int num_points, float score_thres,
+                             float extra_width, float* out_pts_input, int32_t* out_pool_idx, int32_t* out_empty, void* stream) {
+    if (batch < 0 || n < 0 || m < 0 || channels < 0 || num_points < 1 || ld_feat < channels) return ML3D_E_INVALID;
+    if (batch * n > 0x7fffffffll || batch * m > 0x7fffffffll || batch * m * (int64_t)num_points > 0x7fffffffll) return ML3D_E_UNSUPPORTED;
+    if (batch == 0 || m == 0) return 0;
+    if (!rois || !out_pts_input || !out_pool_idx || !out_empty || (n > 0 && (!xyz || !scores || (channels > 0 && !feat))))
+        return ML3D_E_INVALID;
+    RoiPoolArgs A;
+    A.n = n; A.m = m; A.ld_feat = ld_feat; A.c = channels; A.s = num_points; A.score_thres = score_thres; A.extra_width = extra_width;
+    hipLaunchKernelGGL(roi_pool_rows, dim3((unsigned)(batch * m)), dim3(256), 0, (hipStream_t)stream, xyz, feat, scores, rois, A,
+                       out_pts_input, out_pool_idx, out_empty);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

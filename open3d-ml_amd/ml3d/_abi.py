@@ -102,7 +102,7 @@ SYMBOLS = [
     "ml3d_trilinear_devoxelize", "ml3d_segment_max_rows_workspace_bytes", "ml3d_segment_max_rows",
     "ml3d_scn_build_workspace_bytes", "ml3d_scn_build", "ml3d_sparse_conv_bf16x3", "ml3d_scn_bn_relu",
     "ml3d_ball_query", "ml3d_pn2_sa_fused_supported", "ml3d_pn2_sa_mlp_max", "ml3d_pn2_group_rows", "ml3d_pn2_interpolate",
-    "ml3d_bin_decode", "ml3d_rpn_proposals",
+    "ml3d_bin_decode", "ml3d_rpn_proposals", "ml3d_roi_pool",
 ]
 
 
@@ -352,6 +352,8 @@ def bind(lib):
     lib.ml3d_bin_decode.argtypes = [vp, i32, vp, i64, i32, i64, vp, f32, f32, i32, f32, f32, i32, i32, i32, vp, vp]
     lib.ml3d_rpn_proposals.restype = C.c_int
     lib.ml3d_rpn_proposals.argtypes = [vp, vp, i64, i64, i64, i64, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.ml3d_roi_pool.restype = C.c_int
+    lib.ml3d_roi_pool.argtypes = [vp, vp, i64, i32, vp, vp, i64, i64, i64, i32, f32, f32, vp, vp, vp, vp]
     lib.ml3d_vote_update.restype = C.c_int
     lib.ml3d_vote_update.argtypes = [vp, vp, i64, i32, f32, vp, i64, vp]
     lib.ml3d_argmax_labels.restype = C.c_int

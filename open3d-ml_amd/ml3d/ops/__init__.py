@@ -27,4 +27,4 @@ from .pvcnn import (pvcnn_voxel_coords, avg_voxelize, pack_conv3d_weights, conv3
 from .sparseconv import ScnPyramid, scn_build, pack_sparse_weights, sparse_conv, scn_bn_relu   # noqa: F401
 from .pointnet2 import (ball_query, three_nn, three_interpolate, pn2_interpolate, pn2_sa_mlp_max, pack_sa_weights,   # noqa: F401
                         sa_fused)
-from .pointrcnn import bin_decode, rpn_proposals   # noqa: F401
+from .pointrcnn import bin_decode, rpn_proposals, roi_pool   # noqa: F401

@@ -144,21 +144,23 @@ def pack_sa_weights(w_x, b1, w2, b2, w3, b3, nsample):
     return p
 
 
-def _linear_rows(a, w, bias, act, out=None):
-    """``ml3d_linear`` on rows that may be column slices -> act(a w + bias) into ``out`` (may be a column slice)."""
+def _linear_rows(a, w, bias, act, out=None, a2=None):
+    """``ml3d_linear`` on rows that may be column slices -> act([a | a2] w + bias) into ``out`` (may be a column slice)."""
     lib = _abi.get()
     m, k, n = int(a.shape[0]), int(a.shape[1]), int(w.shape[1])
     lda = _rows("pn2 linear", a)
+    lda2, k2 = (0, 0) if a2 is None else (_rows("pn2 linear", a2), int(a2.shape[1]))
     if out is None:
         out = torch.empty((m, n), dtype=torch.float32, device=a.device)
     ldc = _rows("pn2 linear", out, n)
-    if w.shape[0] != k or not w.is_contiguous() or out.shape[0] != m:
+    if w.shape[0] != k + k2 or not w.is_contiguous() or out.shape[0] != m or (a2 is not None and a2.shape[0] != m):
         raise RuntimeError("pn2 linear: inconsistent shapes")
-    wsb = lib.ml3d_linear_workspace_bytes(m, n, k)
+    wsb = lib.ml3d_linear_workspace_bytes(m, n, k + k2)
     ws = _gates._ws(wsb, a.device)
     with torch.cuda.device(a.device):
-        rc = lib.ml3d_linear(a.data_ptr(), lda, k, None, 0, m, None, 0, 0, w.data_ptr(), None if bias is None else bias.data_ptr(),
-                             None, 0, None, 0, 0, int(act), 0.0, out.data_ptr(), ldc, m, n, ws.data_ptr(), wsb, _stream())
+        rc = lib.ml3d_linear(a.data_ptr(), lda, k, None, 0, m, None if a2 is None else a2.data_ptr(), lda2, k2, w.data_ptr(),
+                             None if bias is None else bias.data_ptr(), None, 0, None, 0, 0, int(act), 0.0, out.data_ptr(), ldc, m, n,
+                             ws.data_ptr(), wsb, _stream())
     _abi.check(rc, "ml3d_linear")
     return out
 

@@ -1,6 +1,7 @@
-"""PointRCNN stage-1 ops on the HIP kernels of csrc/pointrcnn.hip (contracts: include/ml3d_hip.h, "PointRCNN stage 1"):
+"""PointRCNN ops on the HIP kernels of csrc/pointrcnn.hip (contracts: include/ml3d_hip.h, "PointRCNN stage 1" / "stage 2"):
 ``bin_decode`` restates the reference's ``decode_bbox_target`` (point_rcnn.py:1153-1272), ``rpn_proposals`` its
-``ProposalLayer.forward`` with ``post_process=True`` (:1020-1150) for a whole batch, without a read-back."""
+``ProposalLayer.forward`` with ``post_process=True`` (:1020-1150) for a whole batch, without a read-back; ``roi_pool`` produces
+the ``pts_input`` rows of ``RCNN.forward`` (:848-887): the wheel's RoI pooling, the two extra columns and the canonical transform."""
 import numpy as np
 import torch
 
@@ -99,4 +100,42 @@ def rpn_proposals(scores, boxes, nms_pre, nms_post, nms_thres, out=None):
     return rois, roi_scores, roi_index
 
 
-__all__ = ["bin_decode", "rpn_proposals", "reg_channels"]
+def roi_pool(xyz, feat, scores, rois, num_points=512, score_thres=0.3, extra_width=1.0, out=None):
+    """``xyz`` [B, N, 3], ``feat`` rows [B * N, C] (may be a column slice of a wider buffer), ``scores`` [B, N] raw, ``rois``
+    [B, M, 7] -> (pts_input [B * M, num_points, 5 + C], pool_idx int32 [B, M, num_points] item-local or -1, empty int32 [B, M]).
+    ``out``: the three tensors to write into."""
+    _need_gpu(xyz, feat, scores, rois, *(out or ()))
+    lib = _abi.get()
+    if xyz.dim() != 3 or xyz.shape[2] != 3 or scores.dim() != 2 or tuple(scores.shape) != tuple(xyz.shape[:2]) or rois.dim() != 3 or \
+            rois.shape[2] != 7 or rois.shape[0] != xyz.shape[0]:
+        raise RuntimeError("roi_pool: invalid argument: xyz [B, N, 3], scores [B, N] and rois [B, M, 7] expected")
+    for t in (xyz, scores, rois):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("roi_pool: invalid argument: float32 contiguous tensors required")
+    b, n, m, s = int(xyz.shape[0]), int(xyz.shape[1]), int(rois.shape[1]), int(num_points)
+    if feat.dim() != 2 or feat.dtype != torch.float32 or feat.shape[0] != b * n or (feat.shape[1] > 1 and feat.stride(1) != 1):
+        raise RuntimeError("roi_pool: invalid argument: feat must be float32 rows [B * N, C] with unit column stride")
+    c = int(feat.shape[1])
+    ld = int(feat.stride(0)) if b * n > 1 else max(int(feat.stride(0)), c)
+    if s < 1 or ld < c:
+        raise RuntimeError("roi_pool: invalid argument: num_points >= 1 and a row stride >= C required")
+    if b * n >= 2 ** 31 or b * m * s >= 2 ** 31:
+        raise RuntimeError("roi_pool: invalid argument: B * N < 2^31 and B * M * num_points < 2^31 required")
+    dev = xyz.device
+    if out is None:
+        out = (torch.empty((b * m, s, 5 + c), dtype=torch.float32, device=dev), torch.empty((b, m, s), dtype=torch.int32, device=dev),
+               torch.empty((b, m), dtype=torch.int32, device=dev))
+    pts_input, pool_idx, empty = out
+    if tuple(pts_input.shape) != (b * m, s, 5 + c) or tuple(pool_idx.shape) != (b, m, s) or tuple(empty.shape) != (b, m) or \
+            pts_input.dtype != torch.float32 or pool_idx.dtype != torch.int32 or empty.dtype != torch.int32 or \
+            not (pts_input.is_contiguous() and pool_idx.is_contiguous() and empty.is_contiguous()):
+        raise RuntimeError("roi_pool: invalid argument: out = (f32 [B * M, S, 5 + C], int32 [B, M, S], int32 [B, M]) contiguous")
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_roi_pool(xyz.data_ptr(), feat.data_ptr(), ld, c, scores.data_ptr(), rois.data_ptr(), b, n, m, s,
+                               float(score_thres), float(extra_width), pts_input.data_ptr(), pool_idx.data_ptr(), empty.data_ptr(),
+                               _stream())
+    _abi.check(rc, "ml3d_roi_pool")
+    return pts_input, pool_idx, empty
+
+
+__all__ = ["bin_decode", "rpn_proposals", "reg_channels", "roi_pool"]

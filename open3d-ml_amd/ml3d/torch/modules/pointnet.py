@@ -152,26 +152,7 @@ class Pointnet2MSG(nn.Module):
     # ---- forward ------------------------------------------------------------------------------------------------------------
     def _sa_level(self, sa, p, xyz, feat, hip):
         """xyz [B, n, 3], feat [B * n, c] or None -> (new_xyz [B, m, 3], new_feat [B * m, sum c3], fps, ball-query indices)."""
-        b, n, m = int(xyz.shape[0]), int(xyz.shape[1]), sa.npoint
-        if m > n:
-            raise ValueError("Pointnet2MSG: a level samples %d of %d points" % (m, n))
-        rows = xyz.view(b * n, 3)
-        rs, nrs = np.arange(b + 1, dtype=np.int64) * n, np.arange(b + 1, dtype=np.int64) * m
-        fps = ops.furthest_point_sampling(rows, rs, nrs, rs, nrs)              # GLOBAL rows
-        new_xyz = rows.index_select(0, fps.long()).view(b, m, 3)
-        idx = pn2_ops.ball_query(xyz, new_xyz, sa.radii, sa.nsamples)
-        out = torch.empty((b * m, sum(s["c3"] for s in p["scales"])), dtype=torch.float32, device=xyz.device)
-        y = ops.linear(feat, p["w1"]) if hip and feat is not None else None      # the feature rows of every scale's first layer
-        o1 = o3 = 0
-        for s, sc in enumerate(p["scales"]):
-            if hip:
-                pn2_ops.pn2_sa_mlp_max(None if y is None else y[:, o1:o1 + sc["c1"]], xyz, new_xyz, idx[s], sc["hip"],
-                                       out=out[:, o3:o3 + sc["c3"]])
-            else:
-                out[:, o3:o3 + sc["c3"]] = _torch_sa(xyz, feat, new_xyz, idx[s], sc["raw"])
-            o1, o3 = o1 + sc["c1"], o3 + sc["c3"]
-        local = fps.view(b, m) - torch.arange(b, dtype=torch.int32, device=fps.device)[:, None] * n
-        return new_xyz, out, local, idx
+        return sa_level(xyz, feat, sa.npoint, sa.radii, sa.nsamples, p, hip, "Pointnet2MSG")
 
     def _fp_level(self, p, unknown, known, skip, known_feat, hip):
         b = int(unknown.shape[0])
@@ -215,6 +196,48 @@ class Pointnet2MSG(nn.Module):
             out = l_feat[0]
             features = None if out is None else out.view(b, n0, -1).transpose(1, 2).contiguous()
         return l_xyz[0], features
+
+
+# ---- one set-abstraction level on rows (Pointnet2MSG and the RCNN stage of PointRCNN) -------------------------------------------
+def sa_level(xyz, feat, npoint, radii, nsamples, p, hip, who="sa_level"):
+    """xyz [B, n, 3], feat [B * n, c] or None, ``p`` = dict(scales=[dict(hip=pack_sa_weights(...), raw=[(w, scale, shift)] * 3, c1,
+    c3)], w1=[c, sum c1]) -> (new_xyz [B, m, 3], new_feat [B * m, sum c3], fps int32 [B, m] item-local, ball-query indices)."""
+    b, n, m = int(xyz.shape[0]), int(xyz.shape[1]), npoint
+    if m > n:
+        raise ValueError("%s: a level samples %d of %d points" % (who, m, n))
+    rows = xyz.view(b * n, 3)
+    rs, nrs = np.arange(b + 1, dtype=np.int64) * n, np.arange(b + 1, dtype=np.int64) * m
+    fps = ops.furthest_point_sampling(rows, rs, nrs, rs, nrs)              # GLOBAL rows
+    new_xyz = rows.index_select(0, fps.long()).view(b, m, 3)
+    idx = pn2_ops.ball_query(xyz, new_xyz, radii, nsamples)
+    out = _sa_scales(xyz, feat, new_xyz, idx, p, hip)
+    local = fps.view(b, m) - torch.arange(b, dtype=torch.int32, device=fps.device)[:, None] * n
+    return new_xyz, out, local, idx
+
+
+def _sa_scales(xyz, feat, new_xyz, idx, p, hip):
+    b, m = int(new_xyz.shape[0]), int(new_xyz.shape[1])
+    out = torch.empty((b * m, sum(s["c3"] for s in p["scales"])), dtype=torch.float32, device=xyz.device)
+    y = ops.linear(feat, p["w1"]) if hip and feat is not None else None      # the feature rows of every scale's first layer
+    o1 = o3 = 0
+    for s, sc in enumerate(p["scales"]):
+        if hip:
+            pn2_ops.pn2_sa_mlp_max(None if y is None else y[:, o1:o1 + sc["c1"]], xyz, new_xyz, idx[s], sc["hip"],
+                                   out=out[:, o3:o3 + sc["c3"]])
+        else:
+            out[:, o3:o3 + sc["c3"]] = _torch_sa(xyz, feat, new_xyz, idx[s], sc["raw"])
+        o1, o3 = o1 + sc["c1"], o3 + sc["c3"]
+    return out
+
+
+def sa_group_all(xyz, feat, p, hip):
+    """The reference's ``GroupAll`` level (pointnet2_utils.py:281; ``npoint=None``): every point of a cloud, RAW xyz (no centre is
+    subtracted), one output row per cloud -- the set-abstraction body with a centre at the origin and the index list 0 .. n - 1.
+    xyz [B, n, 3], feat [B * n, c] -> [B, c3]."""
+    b, n = int(xyz.shape[0]), int(xyz.shape[1])
+    centres = torch.zeros((b, 1, 3), dtype=torch.float32, device=xyz.device)
+    idx = torch.arange(n, dtype=torch.int32, device=xyz.device).expand(b, 1, n).contiguous()
+    return _sa_scales(xyz, feat, centres, [idx], p, hip)
 
 
 # ---- the torch formulation (ML3D_PN2_OPS=torch) --------------------------------------------------------------------------------
