@@ -78,6 +78,13 @@ int grid_build(const float* points, Segs segs, const GridWs& ws, float target_oc
 // sub-cloud): reuses the parent's bounding box and dimension estimate, cell size scaled for the
 // thinner sampling — skips the bbox and occupancy passes.
 int grid_build_derived(const float* points, Segs segs, const GridWs& ws, const GridWs& parent, hipStream_t stream);
+// All `levels` grids of a UNIFORM pyramid (cloud b = rows [b n0, b n0 + n0) of `points`, level l = its prefix of n[l] rows, n[0] = n0,
+// n non-increasing) in ONE launch of one workgroup per cloud: what grid_build(level 0) + grid_build_derived(level l, level 0) build
+// -- the same GridSeg, the same cell-start words a search reads, the same points per cell -- plus, where tile_order[l] is given, the
+// level's cell-sorted sequence of point rows.  ws[l]: the level's workspace (grid_ws(n[l] * batch, batch)).
+constexpr int GRID_PYRAMID_MAX_LEVELS = 8;
+int grid_build_pyramid(const float* points, int64_t batch, int64_t n0, const int64_t* n, const GridWs* ws, int levels,
+                       int32_t* const* tile_order, float target_occ, hipStream_t stream);
 // Build with a caller-chosen cell size (fixed-radius search: cell ~ radius, so a query's box is 3x3x3
 // cells); skips the occupancy probe.  The size is grown until the dense table fits.
 int grid_build_fixed(const float* points, Segs segs, const GridWs& ws, float cell, hipStream_t stream);

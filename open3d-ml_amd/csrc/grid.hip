@@ -9,6 +9,8 @@
 
 #include <math.h>
 
+#include <gfx950_ops.h>
+
 namespace ml3d {
 
 static void grid_sizes(int64_t n_total, int64_t batch, int64_t* total_cells, int64_t* bitmap_words,
@@ -213,9 +215,10 @@ __device__ __forceinline__ bool dims_fit(const float ext[3], float c, int64_t ca
     return true;
 }
 
-__global__ void grid_setup0(Segs S, const unsigned* bbox, GridSeg* segs, int batch) {
-    int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= batch) return;
+// (the bodies of the per-item set-up steps are device functions: the launch chain below runs each as a kernel of one thread
+//  per item, the one-workgroup-per-cloud builder at the end of this file calls them from one thread of the cloud's workgroup)
+// box[0..2] / box[3..5]: the item's ordered-uint min / max (f2ord)
+__device__ __forceinline__ GridSeg setup0_item(const Segs& S, int s, const unsigned* box) {
     GridSeg g;
     int64_t n = seg_len(S, s);
     int64_t pb = seg_begin_packed(S, s);
@@ -224,8 +227,8 @@ __global__ void grid_setup0(Segs S, const unsigned* bbox, GridSeg* segs, int bat
     g.cell_base = (int)(GRID_CAP * pb + (int64_t)GRID_SLACK * s);
     float ext[3], amax = 0.f, emax = 0.f;
     for (int a = 0; a < 3; ++a) {
-        float lo = n > 0 ? ord2f(bbox[6 * s + a]) : 0.f;
-        float hi = n > 0 ? ord2f(bbox[6 * s + 3 + a]) : 0.f;
+        float lo = n > 0 ? ord2f(box[a]) : 0.f;
+        float hi = n > 0 ? ord2f(box[3 + a]) : 0.f;
         g.lo[a] = lo;
         ext[a] = hi - lo;
         emax = fmaxf(emax, ext[a]);
@@ -251,7 +254,13 @@ __global__ void grid_setup0(Segs S, const unsigned* bbox, GridSeg* segs, int bat
     g.dim_est = 2.5f;
     // the probe is a statistic of the cloud's density: a sixteenth (a quarter) of a large (medium) cloud is plenty
     g.probe_stride = n >= 32768 ? 16 : (n >= 8192 ? 4 : 1);
-    segs[s] = g;
+    return g;
+}
+
+__global__ void grid_setup0(Segs S, const unsigned* bbox, GridSeg* segs, int batch) {
+    int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= batch) return;
+    segs[s] = setup0_item(S, s, bbox + 6 * s);
 }
 
 // ---- K3: occupancy probe at GRID_LEVELS power-of-two resolutions ------------------------------
@@ -358,10 +367,8 @@ __device__ __forceinline__ void finish_grid(GridSeg& g, float c, int64_t cap) {
     for (int a = 0; a < 3; ++a) g.dims[a] = d[a];
 }
 
-__global__ void grid_setup1(const unsigned* occ, GridSeg* segs, int batch, float target) {
-    int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= batch) return;
-    GridSeg g = segs[s];
+// occ[0 .. GRID_LEVELS): the item's occupied-cell counts of the probe
+__device__ __forceinline__ void setup1_item(GridSeg& g, const unsigned* occ, float target) {
     int64_t n = g.n;
     float emax = fmaxf(g.ext[0], fmaxf(g.ext[1], g.ext[2]));
     int64_t cap = (int64_t)GRID_CAP * n + GRID_SLACK;
@@ -372,7 +379,7 @@ __global__ void grid_setup1(const unsigned* occ, GridSeg* segs, int batch, float
         float lam_prev = 0.f, lam_cur = 0.f;
         int lsel = -1;
         for (int l = 0; l < GRID_LEVELS; ++l) {
-            unsigned cnt = occ[GRID_LEVELS * s + l];
+            unsigned cnt = occ[l];
             lam_cur = lam_of_occ(n_probe / (float)(cnt > 0u ? cnt : 1u));
             if (lam_cur >= lam_goal) { lsel = l; break; }
             lam_prev = lam_cur;
@@ -389,14 +396,18 @@ __global__ void grid_setup1(const unsigned* occ, GridSeg* segs, int batch, float
         }
     }
     finish_grid(g, c, cap);
+}
+
+__global__ void grid_setup1(const unsigned* occ, GridSeg* segs, int batch, float target) {
+    int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= batch) return;
+    GridSeg g = segs[s];
+    setup1_item(g, occ + GRID_LEVELS * s, target);
     segs[s] = g;
 }
 
-// grid of a thinner subset of the parent's points: same box, c scaled by (n_parent / n)^(1/D)
-__global__ void grid_setup_derived(Segs S, const GridSeg* parent, GridSeg* segs, int batch) {
-    int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= batch) return;
-    GridSeg g = parent[s];
+// grid of a thinner subset of the parent's points: same box, c scaled by (n_parent / n)^(1/D).  g: the parent's item on entry
+__device__ __forceinline__ void setup_derived_item(const Segs& S, int s, GridSeg& g) {
     int64_t n = seg_len(S, s);
     int64_t pb = seg_begin_packed(S, s);
     float ratio = n > 0 ? (float)g.n / (float)n : 1.0f;
@@ -406,6 +417,13 @@ __global__ void grid_setup_derived(Segs S, const GridSeg* parent, GridSeg* segs,
     g.cell_base = (int)(GRID_CAP * pb + (int64_t)GRID_SLACK * s);
     if (n <= 64) c = fmaxf(g.ext[0], fmaxf(g.ext[1], g.ext[2])) * 2.0f;
     finish_grid(g, c, (int64_t)GRID_CAP * n + GRID_SLACK);
+}
+
+__global__ void grid_setup_derived(Segs S, const GridSeg* parent, GridSeg* segs, int batch) {
+    int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= batch) return;
+    GridSeg g = parent[s];
+    setup_derived_item(S, s, g);
     segs[s] = g;
 }
 
@@ -674,6 +692,371 @@ int grid_build_derived(const float* points, Segs S, const GridWs& ws, const Grid
     hipLaunchKernelGGL(grid_setup_derived, dim3((B + 63) / 64), dim3(64), 0, stream, S, parent.segs, ws.segs, B);
     ML3D_LAUNCH_CHECK();
     return grid_sort(points, S, ws, stream);
+}
+
+// ---- all level grids of a uniform pyramid in ONE launch, one workgroup per cloud ----------------------------------------------
+// Workgroup b builds every level grid of cloud b from the box to the last scatter and never reads a word another workgroup
+// wrote: no agent-scope fence, flag, ticket or spin, nothing waits for another workgroup.  What it produces is what the launch
+// chain above produces: the same GridSeg per (level, cloud) -- the set-up steps are the chain's own device functions --, the same
+// cell-start words in the range a search reads and the same points per cell (order inside a cell was and stays arrival order).
+//
+// Only what is read: a search addresses cell_start[cell_base + j] for j in [0, dims[0] dims[1] dims[2]] (knn.hip scan_shell:
+// cs[xa] .. cs[xb + 1] of a row of the chosen grid), so these ncells + 1 words are zeroed, counted and scanned, not the
+// GRID_CAP n + GRID_SLACK words the table reserves for the cloud.  The probe's bitmaps (one bit per cell of the five probed
+// resolutions) are scratch nobody reads afterwards: they sit at the head of the cloud's own level-0 cell range, word-aligned
+// and private whatever n0 is; the level-0 table is laid over them afterwards.
+//
+// Memory rules (the tables stay in global memory, i.e. in the L2 of the workgroup's XCD; LDS holds a few hundred bytes):
+//  * phases are separated by phase_sync(): every wave drains its vector-memory counter (plain stores acknowledged by L2, atomics
+//    performed), then the workgroup barrier;
+//  * table words are only ever written by plain stores and updated by workgroup-scope atomics (which execute in L2); the one
+//    phases that read them, the scan and the scatter, use L1-bypassing loads (ld_agent), so no plain load of a table line ever precedes an
+//    atomic on it in this launch -- not even by another workgroup that ran on the same CU and shares a 128-byte line at the
+//    border of two clouds' ranges;
+//  * the returning atomics of the probe and the histogram, and the scatter's table reads, are issued U at a time before the
+//    first dependent instruction.
+//
+// One atomic per point and level: the histogram's atomic returns the point's arrival rank in its cell, which waits in a scratch
+// word (GridWs::bitmap: more than 1.25 words per point, and this builder's own bitmaps are elsewhere) until the scatter adds the
+// cell's start to it.  The chain pays two (histogram, scatter); one CU performs ~0.15 scattered L2 atomics per ns, which is what
+// bounds this kernel.
+#ifndef ML3D_GRID_PYRAMID_THREADS
+// A/B build (tools/build_variant.sh): 256, 512 or 1024 threads per cloud; the default is the in-step winner
+#define ML3D_GRID_PYRAMID_THREADS 1024
+#endif
+
+struct PyramidArgs {
+    const float* pts;
+    int64_t stride;          // rows between two clouds of the [batch, n0, 3] tensor
+    float target;
+    int levels;
+    int n[GRID_PYRAMID_MAX_LEVELS];
+    GridSeg* segs[GRID_PYRAMID_MAX_LEVELS];
+    int* cells[GRID_PYRAMID_MAX_LEVELS];
+    int* rank[GRID_PYRAMID_MAX_LEVELS];           // n[l] * batch words of scratch (GridWs::bitmap: this builder's bitmaps are elsewhere)
+    float4* sorted[GRID_PYRAMID_MAX_LEVELS];
+    int32_t* order[GRID_PYRAMID_MAX_LEVELS];      // tile order of the level (order_from_grid's output), or null
+};
+
+__device__ __forceinline__ void phase_sync() {
+#ifndef ML3D_HIPEMU
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    __syncthreads();
+}
+
+// the value exists in a register HERE: keeps the compiler from sinking its computation into the (exec-masked) atomic that uses
+// it, where every atomic of a group would wait for its own operands behind the previous one
+__device__ __forceinline__ void pin(int& x) {
+#ifndef ML3D_HIPEMU
+    asm volatile("" : "+v"(x) : : "memory");
+#endif
+}
+
+// atomics on words the workgroup owns for the whole launch
+#ifdef ML3D_HIPEMU
+__device__ __forceinline__ int own_fetch_add(int* p, int v) { return atomicAdd(p, v); }
+__device__ __forceinline__ unsigned own_fetch_or(unsigned* p, unsigned v) { return atomicOr(p, v); }
+#else
+__device__ __forceinline__ int own_fetch_add(int* p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ unsigned own_fetch_or(unsigned* p, unsigned v) { return __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+#endif
+
+__device__ __forceinline__ unsigned wave_umin(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (unsigned)__shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor(v, o));
+    return v;
+}
+
+// a[i] <- base + a[0] + .. + a[i - 1] for i in [0, m), by the whole workgroup, in place: wave w owns a contiguous slice, rows of 256 in
+// which a lane holds four neighbouring elements (one shuffle scan per 256 elements); the wave sums its slice, the slice sums meet
+// in LDS, then the wave scans its slice behind the carry of the slices before it.  R rows are requested together, rows and
+// elements past the end are masked per lane (no wave-uniform branch: the compiler drains the memory counter at every join of
+// one, i.e. once per row); the loads bypass L1 (the words were updated by atomics).
+template <int T>
+__device__ __forceinline__ void block_exclusive_scan(int* a, int m, int base, int* wsum) {
+    constexpr int R = 4, E = 4;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int rows = (m + E * T - 1) / (E * T);
+    const int first = wv * rows * (64 * E) + E * lane;
+    const uint32_t* ua = reinterpret_cast<const uint32_t*>(a);
+    auto load_rows = [&](int r0, int (&v)[R][E]) {
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const int i = first + (r0 + j) * (64 * E) + e;
+                v[j][e] = (r0 + j < rows && i < m) ? (int)ld_agent(ua + i) : 0;
+            }
+    };
+    int tot = 0;
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        int v[R][E];
+        load_rows(r0, v);
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+#pragma unroll
+            for (int e = 0; e < E; ++e) tot += v[j][e];
+    }
+    tot = wave_sum(tot);
+    if (lane == 0) wsum[wv] = tot;
+    __syncthreads();
+    int carry = base;
+    for (int w = 0; w < wv; ++w) carry += wsum[w];
+    for (int r0 = 0; r0 < rows; r0 += R) {
+        int v[R][E];
+        load_rows(r0, v);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            int mine = 0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) mine += v[j][e];
+            const int incl = wave_inclusive_scan(mine) + carry;
+            int run = incl - mine;                   // exclusive prefix of the lane's first element
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const int i = first + (r0 + j) * (64 * E) + e;
+                if (r0 + j < rows && i < m) a[i] = run;
+                run += v[j][e];
+            }
+            carry = __shfl(incl, 63);
+        }
+    }
+}
+
+template <int T>
+__global__ void __launch_bounds__(T) grid_pyramid_cloud(PyramidArgs A) {
+    constexpr int W = T / 64;
+    constexpr int U = 8;             // points a thread has in flight: loads, then (returning) atomics, then stores
+    constexpr int UP = 4;            // the same in the probe, which holds GRID_LEVELS words and masks per point
+    __shared__ unsigned red[W][6];
+    __shared__ unsigned box[6];
+    __shared__ unsigned occ[GRID_LEVELS];
+    __shared__ GridSeg seg;          // the level being built
+    __shared__ GridSeg seg0;         // level 0: parent of every derived level
+    __shared__ int wsum[W];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int batch = gridDim.x;
+    const float* __restrict__ P = A.pts + 3 * ((int64_t)b * A.stride);
+    const int n0 = A.n[0];
+
+    // ---- box of the cloud (ordered-uint domain, as the chain's atomicMin / atomicMax) ----
+    {
+        unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0u, 0u, 0u};
+        for (int i0 = 0; i0 < n0; i0 += T * U) {
+            float v[U][3];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = min(i0 + u * T + tid, n0 - 1);
+                v[u][0] = P[3 * i]; v[u][1] = P[3 * i + 1]; v[u][2] = P[3 * i + 2];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const unsigned o = f2ord(v[u][a]);
+                    mn[a] = min(mn[a], o); mx[a] = max(mx[a], o);
+                }
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const unsigned lo = wave_umin(mn[a]), hi = wave_umax(mx[a]);
+            if (lane == 0) { red[wv][a] = lo; red[wv][3 + a] = hi; }
+        }
+        __syncthreads();
+        if (tid < 6) {
+            unsigned v = red[0][tid];
+            for (int w = 1; w < W; ++w) v = tid < 3 ? min(v, red[w][tid]) : max(v, red[w][tid]);
+            box[tid] = v;
+        }
+        if (tid < GRID_LEVELS) occ[tid] = 0u;
+        __syncthreads();
+        if (tid == 0) {
+            const Segs S = {nullptr, A.stride, (int64_t)n0, batch};
+            seg = setup0_item(S, b, box);
+        }
+        __syncthreads();
+    }
+
+    // ---- occupancy probe at the GRID_LEVELS resolutions: every probe_stride-th point ----
+    {
+        const GridSeg g = seg;
+        unsigned* bm = reinterpret_cast<unsigned*>(A.cells[0] + g.cell_base);
+        int woff[GRID_LEVELS + 1];       // first bitmap word of a resolution: only the words of its dx dy dz cells exist
+        woff[0] = 0;
+#pragma unroll
+        for (int l = 0; l < GRID_LEVELS; ++l) {
+            const int64_t dx = ((g.dims0[0] - 1) >> l) + 1, dy = ((g.dims0[1] - 1) >> l) + 1, dz = ((g.dims0[2] - 1) >> l) + 1;
+            woff[l + 1] = woff[l] + (int)((dx * dy * dz + 31) >> 5);
+        }
+        for (int i = tid; i < woff[GRID_LEVELS]; i += T) bm[i] = 0u;
+        phase_sync();
+        const int ps = g.probe_stride, per = (n0 + ps - 1) / ps;
+        const float inv = 1.0f / g.c0;
+        int cnt[GRID_LEVELS] = {0, 0, 0, 0, 0};
+        for (int j0 = 0; j0 < per; j0 += T * UP) {
+            float v[UP][3];
+#pragma unroll
+            for (int u = 0; u < UP; ++u) {
+                const int64_t i = (int64_t)min(j0 + u * T + tid, per - 1) * ps;
+                v[u][0] = P[3 * i]; v[u][1] = P[3 * i + 1]; v[u][2] = P[3 * i + 2];
+            }
+            unsigned old[UP][GRID_LEVELS], bit[UP][GRID_LEVELS];
+#pragma unroll
+            for (int u = 0; u < UP; ++u) {
+                const bool valid = j0 + u * T + tid < per;
+                const int cx = cell_coord(v[u][0], g.lo[0], inv, g.dims0[0]);
+                const int cy = cell_coord(v[u][1], g.lo[1], inv, g.dims0[1]);
+                const int cz = cell_coord(v[u][2], g.lo[2], inv, g.dims0[2]);
+#pragma unroll
+                for (int l = 0; l < GRID_LEVELS; ++l) {
+                    const int dx = ((g.dims0[0] - 1) >> l) + 1, dy = ((g.dims0[1] - 1) >> l) + 1;
+                    const int id = (cx >> l) + dx * ((cy >> l) + dy * (cz >> l));
+                    bit[u][l] = 1u << (id & 31);
+                    old[u][l] = bit[u][l];           // (a lane past the end counts nothing)
+                    if (valid) old[u][l] = own_fetch_or(&bm[woff[l] + (id >> 5)], bit[u][l]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UP; ++u)
+#pragma unroll
+                for (int l = 0; l < GRID_LEVELS; ++l) cnt[l] += (old[u][l] & bit[u][l]) ? 0 : 1;
+        }
+#pragma unroll
+        for (int l = 0; l < GRID_LEVELS; ++l) {
+            const int c = wave_sum(cnt[l]);
+            if (lane == 0 && c) atomicAdd(&occ[l], (unsigned)c);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            GridSeg h = seg;
+            setup1_item(h, occ, A.target);
+            seg = h;
+            seg0 = h;
+            A.segs[0][b] = h;
+        }
+        __syncthreads();
+    }
+
+    // ---- per level: zero, histogram, scan, scatter (+ tile order), then the next level's derived set-up ----
+    for (int l = 0; l < A.levels; ++l) {
+        const GridSeg g = seg;
+        const int n = A.n[l];
+        int* tab = A.cells[l] + g.cell_base;
+        const int ncells = g.dims[0] * g.dims[1] * g.dims[2];            // <= GRID_CAP n + GRID_SLACK (dims_fit)
+        // the top word (end of the last cell) is stored, never counted.  In a full grid it is the next cloud's word 0, which that
+        // cloud's workgroup writes (with the same final value, its sorted_base): it is left alone then
+        const bool shared_top = ncells == GRID_CAP * n + GRID_SLACK && b + 1 < batch;
+        int* rank = A.rank[l] + (int64_t)b * n;          // a point's arrival rank in its cell, from the histogram to the scatter
+        auto cell_of = [&](const float (&p)[3]) {
+            const int cx = cell_coord(p[0], g.lo[0], g.inv_c, g.dims[0]);
+            const int cy = cell_coord(p[1], g.lo[1], g.inv_c, g.dims[1]);
+            const int cz = cell_coord(p[2], g.lo[2], g.inv_c, g.dims[2]);
+            return cx + g.dims[0] * (cy + g.dims[1] * cz);
+        };
+        auto load_points = [&](int i0, float (&v)[U][3]) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int64_t i = min(i0 + u * T + tid, n - 1);
+                v[u][0] = P[3 * i]; v[u][1] = P[3 * i + 1]; v[u][2] = P[3 * i + 2];
+            }
+        };
+        // word j counts cell j -- the count a point's atomic returns is its rank in the cell --, then becomes the cell's start in the
+        // scan; the scatter only READS the starts: one atomic per point and level, not two
+        for (int i = tid; i < ncells; i += T) tab[i] = 0;
+        if (tid == 0 && !shared_top) tab[ncells] = g.sorted_base + n;
+        phase_sync();
+        for (int i0 = 0; i0 < n; i0 += T * U) {
+            float v[U][3];
+            load_points(i0, v);
+            // every cell first (one wait for the U loads), then the U returning atomics back to back, then one wait and the stores
+            int cid[U], r[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) cid[u] = cell_of(v[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) pin(cid[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                r[u] = 0;
+                if (i0 + u * T + tid < n) r[u] = own_fetch_add(&tab[cid[u]], 1);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) pin(r[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (i0 + u * T + tid < n) rank[i0 + u * T + tid] = r[u];
+        }
+        phase_sync();
+        block_exclusive_scan<T>(tab, ncells, g.sorted_base, wsum);
+        phase_sync();
+        float4* __restrict__ sorted = A.sorted[l];
+        int32_t* __restrict__ order = A.order[l];
+        const uint32_t* utab = reinterpret_cast<const uint32_t*>(tab);
+        const uint32_t* urank = reinterpret_cast<const uint32_t*>(rank);
+        for (int i0 = 0; i0 < n; i0 += T * U) {
+            float v[U][3];
+            load_points(i0, v);
+            int cid[U], pos[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) pos[u] = (int)ld_agent(urank + min(i0 + u * T + tid, n - 1));
+#pragma unroll
+            for (int u = 0; u < U; ++u) cid[u] = cell_of(v[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) pin(cid[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) pos[u] += (int)ld_agent(utab + cid[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) pin(pos[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int local = i0 + u * T + tid;
+                if (local >= n) continue;
+                sorted[pos[u]] = make_float4(v[u][0], v[u][1], v[u][2], __int_as_float(local));
+                if (order) order[pos[u]] = b * n + local;
+            }
+        }
+        if (l + 1 < A.levels) {
+            // (every thread took its copy of seg before this level's first barrier)
+            if (tid == 0) {
+                GridSeg h = seg0;
+                const Segs S = {nullptr, A.stride, (int64_t)A.n[l + 1], batch};
+                setup_derived_item(S, b, h);
+                seg = h;
+                A.segs[l + 1][b] = h;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+int grid_build_pyramid(const float* points, int64_t batch, int64_t n0, const int64_t* n, const GridWs* ws, int levels,
+                       int32_t* const* tile_order, float target_occ, hipStream_t stream) {
+    if (batch <= 0 || levels <= 0) return 0;
+    if (levels > GRID_PYRAMID_MAX_LEVELS || n[0] != n0) return -3;
+    PyramidArgs A = {};
+    A.pts = points;
+    A.stride = n0;
+    A.target = target_occ > 0.f ? target_occ : 4.0f;
+    for (int l = 0; l < levels && n[l] > 0; ++l) {          // (level l + 1 is a prefix of level l: behind an empty level all are empty)
+        A.n[l] = (int)n[l];
+        A.segs[l] = ws[l].segs;
+        A.cells[l] = ws[l].cells;
+        A.rank[l] = reinterpret_cast<int*>(ws[l].bitmap);
+        A.sorted[l] = ws[l].sorted;
+        A.order[l] = tile_order ? tile_order[l] : nullptr;
+        A.levels = l + 1;
+    }
+    if (A.levels == 0) return 0;
+    constexpr int T = ML3D_GRID_PYRAMID_THREADS;
+    static_assert(T == 256 || T == 512 || T == 1024, "one cloud's workgroup: 256, 512 or 1024 threads");
+    hipLaunchKernelGGL((grid_pyramid_cloud<T>), dim3((unsigned)batch), dim3(T), 0, stream, A);
+    ML3D_LAUNCH_CHECK();
+    return 0;
 }
 
 }  // namespace ml3d

@@ -484,6 +484,30 @@ __global__ void order_from_grid(const float4* __restrict__ sorted, int64_t n_tot
 // the library reads nothing from the environment and keeps no process-wide state.
 static constexpr float tuning_occ() { return 0.f; }
 
+#ifndef ML3D_GRID_PYRAMID_FUSED
+// A/B switch (build time).  1 = the pyramid's grids come from grid_build_pyramid (one launch, one workgroup per cloud) where the
+// arguments admit it; 0 = always the launch chain (grid_build + grid_build_derived + order_from_grid per level).
+#define ML3D_GRID_PYRAMID_FUSED 1
+#endif
+// Which builder a pyramid call takes: a function of the arguments alone (its clouds are uniform by construction).  One workgroup
+// walks a whole cloud, so the launch lasts as long as one cloud takes whatever the batch is (a one-cloud call of 45 056 points: 0.59 ms against 0.30), while the
+// chain's passes spread every cloud over the chip.  Measured per call, chain against builder (profiles/r07_pyramid_build_sweep.log,
+// 45 056 points): -0.29 ms at batch 1, -0.28 at 4, -0.07 at 32, +0.03 at 48, +0.11 at 64, +0.41 at 128, +0.96 at 256; at batch 128
+// and 256 the builder wins at every cloud size measured, 16 384 to 131 072 points.  So: at least 48 clouds, at most 131 072 points
+// (the largest size measured); everything else keeps the chain.  (The macros are the A/B and sweep builds' handles.)
+#ifndef ML3D_GRID_PYRAMID_MAX_N0
+#define ML3D_GRID_PYRAMID_MAX_N0 131072
+#endif
+#ifndef ML3D_GRID_PYRAMID_MIN_BATCH
+#define ML3D_GRID_PYRAMID_MIN_BATCH 48
+#endif
+constexpr int64_t GRID_PYRAMID_MAX_N0 = ML3D_GRID_PYRAMID_MAX_N0;
+constexpr int64_t GRID_PYRAMID_MIN_BATCH = ML3D_GRID_PYRAMID_MIN_BATCH;
+static_assert(KNN_MAX_JOBS <= GRID_PYRAMID_MAX_LEVELS, "a pyramid level is a k-NN job");
+static bool pyramid_build_fused(int64_t batch, int64_t n0) {
+    return (ML3D_GRID_PYRAMID_FUSED) && n0 <= GRID_PYRAMID_MAX_N0 && batch >= GRID_PYRAMID_MIN_BATCH;
+}
+
 }  // namespace ml3d
 
 using namespace ml3d;
@@ -589,7 +613,20 @@ extern "C" int ml3d_randla_knn_pyramid_ordered(const float* points, int64_t batc
     if (!ws_carve(workspace, workspace_bytes, &hand, pyramid_ws, batch, num_layers, n, ws)) return ML3D_E_WORKSPACE;
     float occ = tuning_occ();
     // grids of the searched levels: level l = prefix [:n_l] of each cloud (randlanet.py:222)
-    for (int l = 0; l < num_layers; ++l) {
+    const bool fused = pyramid_build_fused(batch, n0);
+    if (fused) {
+        // one launch, one workgroup per cloud (grid.hip).  Trace: the launch is tag 100's; the other levels' events are recorded
+        // back to back behind it (their solo times read ~0: the whole build is level 0's figure)
+        tb(100);
+        if (grid_build_pyramid(points, batch, n0, n, ws, num_layers, tile_order_host, occ, st)) return ML3D_E_LAUNCH;
+        te(100);
+        for (int l = 1; l < num_layers; ++l) {
+            if (n[l] == 0) continue;
+            tb(100 + l);
+            te(100 + l);
+        }
+    }
+    for (int l = 0; !fused && l < num_layers; ++l) {          // the launch chain
         if (n[l] == 0) continue;
         Segs S = {nullptr, n0, n[l], (int)batch};
         tb(100 + l);
