@@ -613,6 +613,25 @@ int ml3d_iou_3d(const float* boxes_a, const float* boxes_b, int64_t n, int64_t m
 /*   numpy promotion of ml3d/torch/models/randlanet.py:420-421, 457-462        */
 /*   (float16 product, float32 sum, float16 store).  inds must be distinct    */
 /*   (the caller keeps the last occurrence of a repeated point).               */
+/* ml3d_vote_project: the finish of a cloud -- that accumulator taken through  */
+/*   proj_inds to the FULL cloud: np.argmax(votes, 1)[proj] and votes[proj].   */
+/*   Inputs: votes_f16 float16 [n_sub, num_classes] row-major,                 */
+/*   1 <= num_classes <= 256; proj_inds[i] in [0, n_sub) -- the caller's duty, */
+/*   NOT checked on the device; repeats and unreferenced rows are normal.      */
+/*   Labels: out_labels[i] = argmax over c of votes[proj_inds[i], c], compared */
+/*   as the exactly converted float32; the FIRST maximum; NaN counts as the    */
+/*   maximum and the first NaN wins (np.argmax's rule and ml3d_argmax_labels'); */
+/*   +0 and -0 are equal.                                                      */
+/*   Scores: out_scores_f16[i, :] = votes[proj_inds[i], :] copied bit for bit  */
+/*   (NaN payloads and -0 preserved); may be NULL: only labels are written.    */
+/*   Alignment: votes_f16 and out_scores_f16 are only 2-byte aligned (a row    */
+/*   slice of a larger buffer starts a * num_classes halves into it: odd for   */
+/*   every odd a with 19 classes); no 4-byte alignment of a base or of a row   */
+/*   is assumed.                                                               */
+/*   n_full == 0 returns 0 and launches nothing; n_sub == 0 with n_full > 0,   */
+/*   NULL pointers (but out_scores_f16), num_classes out of range and n_full   */
+/*   or n_sub >= 2^31 are invalid (-1, before any HIP call).                   */
+/*   One launch, no workspace, no atomics, deterministic.                      */
 /* ------------------------------------------------------------------------- */
 size_t ml3d_nearest_to_center_workspace_bytes(int64_t n_points);
 
@@ -622,6 +641,10 @@ int ml3d_nearest_to_center(const float* points, int64_t n_points, const float* c
 
 int ml3d_vote_update(const float* logits, const int32_t* point_inds, int64_t n, int num_classes,
                      float smooth, void* probs_f16, int64_t n_cloud, void* stream);
+
+int ml3d_vote_project(const void* votes_f16, int64_t n_sub, int num_classes,
+                      const int32_t* proj_inds, int64_t n_full,
+                      uint8_t* out_labels, void* out_scores_f16, void* stream);
 
 /* ---- the patch loop of one cloud with NOTHING read back (ABI 5) ------------------------------- */
 /* The sampler + transform of a test cloud (semseg_spatially_regular.py:64-111,                    */

@@ -734,6 +734,57 @@ vote_update(const float* __restrict__ logits, const int32_t* __restrict__ inds, 
     }
 }
 
+// the finish of a cloud: the float16 votes of the sub-cloud taken through proj to the FULL cloud, labels and scores in one launch.
+// A workgroup owns VP_ROWS consecutive output rows.  Their scores are ONE contiguous run of rows * C halves, so the lanes walk that
+// run dword by dword -- lane l of a wave writes the l-th dword, 256 consecutive bytes per wave and store -- and each half of a dword
+// is fetched by its own 2-byte load from votes[proj[row], col]: 2-byte loads are the one access that is legal at every base and
+// every row pitch (an odd C makes every second row 2-byte aligned only), and the gathered rows are whole 38-byte runs that the
+// neighbouring lanes consume, so every fetched line is used.  A run that starts on an odd half (the base of a row slice) gets
+// its first half, and one that then ends on one its last, from lane 0 as 2-byte stores.  Then one lane per row takes the first
+// maximum of its source row (the lines are in L1/L2 from the copy) and writes the label byte: 128 consecutive bytes per workgroup.
+constexpr int VP_ROWS = 128;
+
+__device__ __forceinline__ float vp_float(unsigned short bits) {
+    __half h;
+    __builtin_memcpy(&h, &bits, 2);
+    return __half2float(h);                                     // exact
+}
+
+__global__ void __launch_bounds__(VP_ROWS)
+vote_project(const unsigned short* __restrict__ votes, int C, const int32_t* __restrict__ proj, int64_t n_full,
+             uint8_t* __restrict__ out_labels, unsigned short* __restrict__ out_scores) {
+    const int64_t r0 = (int64_t)blockIdx.x * VP_ROWS;
+    const int rows = (int)((n_full - r0) < VP_ROWS ? (n_full - r0) : VP_ROWS);
+    if (out_scores) {
+        unsigned short* dst = out_scores + r0 * C;              // 2-byte aligned, no more
+        const int total = rows * C;                             // <= 128 * 256 halves
+        const int head = (int)((reinterpret_cast<uintptr_t>(dst) >> 1) & 1);      // halves before the first 4-byte boundary
+        const int n2 = (total - head) / 2;
+        uint32_t* d2 = reinterpret_cast<uint32_t*>(dst + head);
+        for (int q = threadIdx.x; q < n2; q += VP_ROWS) {
+            const int e = head + 2 * q;
+            const int r = e / C, c = e - r * C;
+            const unsigned short* src = votes + (int64_t)proj[r0 + r] * C;
+            const uint32_t lo = src[c];
+            const uint32_t hi = c + 1 < C ? src[c + 1] : votes[(int64_t)proj[r0 + r + 1] * C];
+            d2[q] = lo | (hi << 16);
+        }
+        if (threadIdx.x == 0) {
+            if (head) dst[0] = votes[(int64_t)proj[r0] * C];
+            if (head + 2 * n2 < total) dst[total - 1] = votes[(int64_t)proj[r0 + rows - 1] * C + C - 1];
+        }
+    }
+    if ((int)threadIdx.x >= rows) return;
+    const unsigned short* row = votes + (int64_t)proj[r0 + threadIdx.x] * C;
+    float best = vp_float(row[0]);
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = vp_float(row[c]);
+        if ((v > best || v != v) && !(best != best)) { best = v; arg = c; }
+    }
+    out_labels[r0 + threadIdx.x] = (uint8_t)arg;
+}
+
 // labels = argmax over the classes (first maximum, NaN counts as the maximum -- torch.argmax), one thread per point
 __global__ void __launch_bounds__(256)
 argmax_rows(const float* __restrict__ scores, int64_t n, int C, uint8_t* __restrict__ out) {
@@ -949,5 +1000,16 @@ extern "C" int ml3d_vote_update(const float* logits, const int32_t* point_inds, 
     if (!logits || !point_inds || !probs_f16) return ML3D_E_INVALID;
     hipLaunchKernelGGL(vote_update, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, point_inds, n,
                        num_classes, smooth, (__half*)probs_f16, n_cloud);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" int ml3d_vote_project(const void* votes_f16, int64_t n_sub, int num_classes, const int32_t* proj_inds, int64_t n_full,
+                                 uint8_t* out_labels, void* out_scores_f16, void* stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_full < 0 || n_sub < 0 || n_full >= lim || n_sub >= lim || num_classes <= 0 || num_classes > 256) return ML3D_E_INVALID;
+    if (n_full == 0) return 0;
+    if (n_sub == 0 || !votes_f16 || !proj_inds || !out_labels) return ML3D_E_INVALID;
+    hipLaunchKernelGGL(vote_project, dim3((unsigned)((n_full + VP_ROWS - 1) / VP_ROWS)), dim3(VP_ROWS), 0, (hipStream_t)stream,
+                       (const unsigned short*)votes_f16, num_classes, proj_inds, n_full, out_labels, (unsigned short*)out_scores_f16);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

@@ -335,3 +335,37 @@ def vote_update(test_probs, point_inds, logits, smooth=0.95):
                                   test_probs.shape[0], _stream())
     _abi.check(rc, "ml3d_vote_update")
     return test_probs
+
+
+def vote_project(votes, proj_inds, out_labels=None, out_scores=None, scores=True):
+    """The finish of a cloud on the device: the float16 vote accumulator ``votes`` [n_sub, C <= 256] taken through ``proj_inds``
+    (int32 [n_full], every entry in [0, n_sub) -- the caller's duty, not checked) to the FULL cloud.  Returns
+    ``(uint8 [n_full] = np.argmax(votes, 1)[proj_inds]`` -- first maximum, the first NaN wins -- ``, float16 [n_full, C] =
+    votes[proj_inds]`` bit for bit, or None with ``scores=False``).  ``votes`` and ``out_scores`` may be row slices of larger
+    contiguous buffers: nothing beyond 2-byte alignment is assumed.  One launch (``ml3d_vote_project``)."""
+    lib = _abi.get()
+    _need_gpu(votes, proj_inds)
+    if votes.dtype != torch.float16 or votes.dim() != 2 or not votes.is_contiguous() or not (1 <= votes.shape[1] <= 256):
+        raise RuntimeError("vote_project: votes must be a contiguous float16 [n_sub, classes] tensor with 1 <= classes <= 256")
+    if proj_inds.dtype != torch.int32 or proj_inds.dim() != 1 or not proj_inds.is_contiguous():
+        raise RuntimeError("vote_project: proj_inds must be a contiguous int32 [n_full] tensor")
+    n_sub, C_ = int(votes.shape[0]), int(votes.shape[1])
+    n_full = int(proj_inds.numel())
+    if n_full and not n_sub:
+        raise RuntimeError("vote_project: no votes to project")
+    dev = votes.device
+    if out_labels is None:
+        out_labels = torch.empty(n_full, dtype=torch.uint8, device=dev)
+    elif out_labels.dtype != torch.uint8 or out_labels.numel() != n_full or not out_labels.is_contiguous():
+        raise RuntimeError("vote_project: out_labels must be a contiguous uint8 tensor with one entry per point")
+    if not scores:
+        out_scores = None
+    elif out_scores is None:
+        out_scores = torch.empty((n_full, C_), dtype=torch.float16, device=dev)
+    elif out_scores.dtype != torch.float16 or tuple(out_scores.shape) != (n_full, C_) or not out_scores.is_contiguous():
+        raise RuntimeError("vote_project: out_scores must be a contiguous float16 [n_full, classes] tensor")
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_vote_project(votes.data_ptr(), n_sub, C_, proj_inds.data_ptr(), n_full, out_labels.data_ptr(),
+                                   None if out_scores is None else out_scores.data_ptr(), _stream())
+    _abi.check(rc, "ml3d_vote_project")
+    return out_labels, out_scores

@@ -29,6 +29,7 @@ class GpuSearchTree:
         self.device = torch.device(device)
         self._dev = None
         self._host = None
+        self.proj_dev = None       # ``preprocess``: the device copy of the cloud's ``proj_inds`` (int32), read by the device finish
         if host_index:
             from sklearn.neighbors import KDTree      # the reference's own dependency (randlanet.py:8, kpconv.py:9)
             self._host = KDTree(self.data)
@@ -40,6 +41,7 @@ class GpuSearchTree:
 
     def __setstate__(self, st):
         self.data, self.device, self._host, self._dev = st['data'], torch.device(st['device']), st['host'], None
+        self.proj_dev = None
 
     def _pts(self):
         if self._dev is None:
@@ -101,6 +103,7 @@ def preprocess_segmentation(data, attr, grid_size, device, proj_splits=("test", 
     if attr['split'] in proj_splits:
         proj = ops.knn_search(sub_points, p, 1).neighbors_index
         out['proj_inds'] = proj.reshape(-1).cpu().numpy().astype(np.int32)
+        tree.proj_dev = proj.reshape(-1).to(torch.int32).contiguous()     # (on the tree: the dict's keys are the reference's)
     return out
 
 

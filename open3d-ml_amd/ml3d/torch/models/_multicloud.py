@@ -6,14 +6,19 @@ import numpy as np
 import torch
 
 from ... import _abi
+from ... import ops
+
+FINISHES = ("device", "host")
 
 
-def check_many_args(name, model, n_clouds, max_in_flight, seeds, draw_seeds):
+def check_many_args(name, model, n_clouds, max_in_flight, seeds, draw_seeds, finish="host"):
     """The checks every ``inference_many`` starts with, messages prefixed ``name``.  Returns (max_in_flight as int, the seeds);
     ``draw_seeds(n_clouds)`` is the model's own default for ``seeds=None``."""
     _abi.require_gpu(model.device, name)
     if model.training:
         raise RuntimeError(name + ": call model.eval() first")
+    if finish not in FINISHES:
+        raise ValueError(name + ": finish must be 'device' or 'host'")
     S = int(max_in_flight)
     if S < 1 or S > 256:
         raise ValueError(name + ": 1 <= max_in_flight <= 256")
@@ -24,6 +29,17 @@ def check_many_args(name, model, n_clouds, max_in_flight, seeds, draw_seeds):
     return S, seeds
 
 
+def finish_cloud(votes, proj_inds, proj_dev=None):
+    """The finish of the single-cloud loops (``inference_end``), synchronous: the float16 device ``votes`` through ``proj_inds`` by
+    ``ops.vote_project`` -> ``{'predict_labels': int64, 'predict_scores': float16}``, the arrays ``np.argmax(probs, 1)[proj_inds]`` and
+    ``probs[proj_inds]`` are.  ``proj_dev``: the device copy of ``proj_inds`` (int32) where the caller has one; else one upload."""
+    proj = proj_dev
+    if proj is None:
+        proj = torch.from_numpy(np.ascontiguousarray(proj_inds, dtype=np.int32).reshape(-1)).to(votes.device)
+    labels, scores = ops.vote_project(votes, proj)
+    return {'predict_labels': labels.cpu().numpy().astype(np.int64), 'predict_scores': scores.cpu().numpy()}
+
+
 class CloudSlots:
     """Up to ``max_in_flight`` clouds advancing in lock step.  ``slots[s]`` is the state dict of the cloud in slot s (None once
     retired with no cloud left to take its place); ``buf`` holds the concatenation over the slots of the clouds' ``points``,
@@ -32,11 +48,18 @@ class CloudSlots:
 
     ``admit()`` returns the next cloud's state -- a dict with ``n``, ``proj_inds``, the four per-point device tensors but the votes,
     ``feat`` and whatever the model counts per cloud -- or None when no cloud is left; ``retired(state, result, possibility)``
-    receives a finished cloud's state, its ``{'predict_labels', 'predict_scores'}`` and its final possibilities (numpy)."""
+    receives a finished cloud's state, its ``{'predict_labels', 'predict_scores'}`` and its final possibilities (numpy).
+    ``finish='device'``: a finished cloud's votes are projected by ``ops.vote_project`` and copied out on a copy stream, and
+    ``retired`` is called from ``poll()`` -- the loop calls it where it reads back its minima -- or ``drain()`` -- before the loop
+    returns -- once the copies have completed; the state may carry ``proj_dev``, the device copy of ``proj_inds`` (int32).
+    ``finish='host'``: ``retired`` is called from within ``replace_finished``."""
     ARRAYS = ('points', 'possibility', 'label', 'votes')
 
-    def __init__(self, max_in_flight, admit, retired, device, num_classes):
+    def __init__(self, max_in_flight, admit, retired, device, num_classes, finish="host"):
         self._admit, self._retired, self.device, self.num_classes = admit, retired, device, int(num_classes)
+        self.finish = finish
+        self._copy = None                      # the ONE extra stream, made by the first device retire
+        self._pending, self._free = [], []     # retires on their way out, oldest first; staging buffers whose copies have completed
         self.slots, self.buf, self.splits = [], {}, np.zeros(1, np.int64)
         while len(self.slots) < max_in_flight:
             st = self.admit()
@@ -81,7 +104,8 @@ class CloudSlots:
         self.buf, self.splits = new, splits
 
     def retire(self, slot):
-        """Empty ``slot``: (the cloud's state, its result from its votes through its ``proj_inds``, its final possibilities)."""
+        """The ``finish='host'`` route, blocking.  Empty ``slot``: (the cloud's state, its result from its votes through its
+        ``proj_inds``, its final possibilities)."""
         st = self.slots[slot]
         a, b = self.rows(slot)
         probs = self.buf['votes'][a:b].cpu().numpy()
@@ -89,13 +113,83 @@ class CloudSlots:
         self.slots[slot] = None
         return st, result, self.buf['possibility'][a:b].cpu().numpy()
 
+    def _staging(self, n_full, n_sub):
+        """Pinned host buffers for one retire (device-to-host copies go through pinned memory, like ``PinnedUpload``'s uploads): a
+        set from ``_free`` -- sets whose copies' event HAS completed, no other is ever handed out again -- or a new one."""
+        for i, sg in enumerate(self._free):
+            if sg['labels'].numel() >= n_full and sg['possibility'].numel() >= n_sub:
+                return self._free.pop(i)
+        room = lambda n: 1 << int(max(n, 1) - 1).bit_length()
+        return dict(labels=torch.empty(room(n_full), dtype=torch.uint8).pin_memory(),
+                    scores=torch.empty(room(n_full) * self.num_classes, dtype=torch.float16).pin_memory(),
+                    possibility=torch.empty(room(n_sub), dtype=torch.float64).pin_memory())
+
+    def retire_async(self, slot):
+        """The ``finish='device'`` route.  Empty ``slot`` without stopping the loop: one ``ops.vote_project`` over the cloud's rows on
+        the current stream, then the copies of labels, scores and possibilities into pinned staging on the copy stream behind an
+        event.  ``poll()`` / ``drain()`` hand the result to ``retired``."""
+        st = self.slots[slot]
+        a, b = self.rows(slot)
+        proj = st.get('proj_dev')
+        if proj is None:                        # (a tree that came out of a pickle keeps host state only: one upload)
+            proj = torch.from_numpy(np.ascontiguousarray(st['proj_inds'], dtype=np.int32).reshape(-1)).to(self.device)
+        votes, poss = self.buf['votes'][a:b], self.buf['possibility'][a:b]
+        n_full, n_sub, C_ = int(proj.numel()), b - a, self.num_classes
+        labels, scores = ops.vote_project(votes, proj)
+        ready = torch.cuda.Event()
+        ready.record()                          # behind the projection and every round that wrote these possibilities
+        if self._copy is None:
+            self._copy = torch.cuda.Stream(self.device)
+        sg = self._staging(n_full, n_sub)
+        with torch.cuda.stream(self._copy):
+            self._copy.wait_event(ready)
+            sg['labels'][:n_full].copy_(labels, non_blocking=True)
+            sg['scores'][:n_full * C_].copy_(scores.reshape(-1), non_blocking=True)
+            sg['possibility'][:n_sub].copy_(poss, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self._copy)
+        self.slots[slot] = None
+        # rebuild() replaces the concatenated buffers right after this, and the caching allocator hands a freed block to the next
+        # request of the CURRENT stream while the copy stream may still be reading it: the entry keeps ``labels``, ``scores`` and the
+        # ``poss`` view (hence the old possibility buffer) referenced until ``done`` has completed, so nothing is freed early.
+        # ``record_stream`` as well, for the one case in which the entry does not live that long: a loop left by an exception
+        # (``on_batch`` may raise) drops the table with copies on their way.
+        for src in (labels, scores, poss):
+            src.record_stream(self._copy)
+        self._pending.append(dict(done=done, state=st, staging=sg, n_full=n_full, n_sub=n_sub, keep=(labels, scores, poss, proj)))
+
+    def _deliver(self, p):
+        """``p['done']`` has completed: copy the arrays out of the staging buffers (the results OWN their memory; the buffers go
+        back to ``_free``, and only now) and hand them to ``retired``."""
+        sg, n_full, n_sub, C_ = p['staging'], p['n_full'], p['n_sub'], self.num_classes
+        result = {'predict_labels': sg['labels'][:n_full].numpy().astype(np.int64),              # (astype copies)
+                  'predict_scores': sg['scores'][:n_full * C_].numpy().reshape(n_full, C_).copy()}
+        possibility = sg['possibility'][:n_sub].numpy().copy()
+        p['keep'] = None
+        self._free.append(sg)
+        self._retired(p['state'], result, possibility)
+
+    def poll(self):
+        """Hand over every retire whose copies have completed, oldest first, without waiting for any."""
+        while self._pending and self._pending[0]['done'].query():
+            self._deliver(self._pending.pop(0))
+
+    def drain(self):
+        """Wait for and hand over every retire still on its way."""
+        while self._pending:
+            self._pending[0]['done'].synchronize()
+            self._deliver(self._pending.pop(0))
+
     def replace_finished(self, finished):
         """Retire the slots ``finished`` and admit the next waiting clouds into them.  True when a cloud was admitted and the
         arrays were rebuilt (one device copy per admission, not per round); otherwise the freed slots keep their rows until the
         next admission and only ``active()`` leaves them out."""
         admitted = False
         for s_ in finished:
-            self._retired(*self.retire(s_))
+            if self.finish == "device":
+                self.retire_async(s_)
+            else:
+                self._retired(*self.retire(s_))
             st = self.admit()
             if st is not None:
                 self.slots[s_] = st

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from ... import _abi
 from ... import ops
-from ._multicloud import CloudSlots, PinnedUpload, check_many_args
+from ._multicloud import CloudSlots, PinnedUpload, check_many_args, finish_cloud
 
 
 class _Cfg(dict):
@@ -741,6 +741,7 @@ class KPFCNN(nn.Module):
         self.inference_ori_data = data
         self.inference_data = self.preprocess(data, attr)
         self.inference_proj_inds = self.inference_data['proj_inds']
+        self._inference_proj_dev = getattr(self.inference_data['search_tree'], 'proj_dev', None)
         num_points = self.inference_data['search_tree'].data.shape[0]
         self.possibility = np.random.rand(num_points) * 1e-3
         self.test_probs = torch.zeros((num_points, self.cfg.num_classes), dtype=torch.float16, device=self.device)
@@ -774,9 +775,8 @@ class KPFCNN(nn.Module):
     def inference_end(self, inputs, results):
         self.update_probs(inputs, results, self.test_probs)
         if np.min(self.possibility) > 0.5:
-            probs = self.test_probs.cpu().numpy()
-            pred_labels = np.argmax(probs, 1)[self.inference_proj_inds]
-            self.inference_result = {'predict_labels': pred_labels, 'predict_scores': probs[self.inference_proj_inds]}
+            # np.argmax(probs, 1)[proj_inds] and probs[proj_inds] of the reference, taken on the device (ml3d_vote_project)
+            self.inference_result = finish_cloud(self.test_probs, self.inference_proj_inds, getattr(self, '_inference_proj_dev', None))
             return True
         return False
 
@@ -848,7 +848,7 @@ class KPFCNN(nn.Module):
         finally:
             np.random.set_state(state)
 
-    def inference_many(self, clouds, seeds=None, max_in_flight=8, on_batch=None):
+    def inference_many(self, clouds, seeds=None, max_in_flight=8, on_batch=None, finish="host"):
         """Segment a list of raw clouds (dicts as ``inference_begin`` takes) with up to ``max_in_flight`` of them advancing in lock
         step.  One SUB-ROUND cuts the next input sphere of every cloud whose batch is not complete: one ``ops.possibility_argmin``,
         one ``ops.sphere_select``, ONE read-back (the sphere sizes and, for clouds at a batch boundary, the minima of the finished
@@ -865,11 +865,16 @@ class KPFCNN(nn.Module):
         sphere held fewer than 2 points) and the final ``possibility`` (numpy float64).
         The single-cloud loop serves, one cloud after the other: every cloud when the sampler is not this class's device one
         (``sampler_index='sklearn'``, a user-set ``trans_point_sampler``) or ``t_normalize.normalize_points`` is on (its whole-array
-        ``mean()`` is a pairwise sum), and a cloud with fewer than 2 points after preprocessing."""
+        ``mean()`` is a pairwise sum), and a cloud with fewer than 2 points after preprocessing.
+        ``finish``: where a finished cloud's votes become its result.  ``"host"``: a blocking read-back, ``np.argmax`` and two gathers
+        on the host with the loop standing still; ``"device"``: one ``ops.vote_project`` and copies on a copy stream while the loop
+        goes on.  The results are equal.  The default is ``"host"``: on this loop's measured workload (tiles of ~25 000 raw points)
+        the device route's medians lay inside the spread of the host route's and of the parent revision's runs
+        (profiles/multicloud_finish_bench.md), unlike RandLA-Net's, whose default is ``"device"``."""
         import time
         cfg, n_clouds = self.cfg, len(clouds)
         S, seeds = check_many_args("KPFCNN.inference_many", self, n_clouds, max_in_flight, seeds,
-                                   lambda n: [int(v) for v in np.random.randint(0, 2 ** 31 - 1, size=n)])
+                                   lambda n: [int(v) for v in np.random.randint(0, 2 ** 31 - 1, size=n)], finish)
         norm = cfg.get('t_normalize', {})
         method = norm.get('method', None)
         axes = [int(a) for a in norm.get('recentering', [0, 1, 2])]
@@ -899,7 +904,7 @@ class KPFCNN(nn.Module):
                 groups.setdefault(width(c), []).append(i)
         for n_extra, members in groups.items():
             self._many_device_loop(clouds, seeds, members, n_extra, S, on_batch, results, info, stats, host_path,
-                                   dict(cap=cap, want=want, n_pool=n_pool, axes=axes, linear=linear, bias=bias, scale=scale), time)
+                                   dict(finish=finish, cap=cap, want=want, n_pool=n_pool, axes=axes, linear=linear, bias=bias, scale=scale), time)
         for i in sorted(host_path):
             results[i], info[i] = self._single_cloud_run(clouds[i], seeds[i])
         return results
@@ -924,7 +929,7 @@ class KPFCNN(nn.Module):
                 feat = None
                 if n_extra:
                     feat = torch.from_numpy(np.ascontiguousarray(data['feat'], dtype=np.float32)).to(dev)
-                return dict(cloud=i, rng=rng, n=n, proj_inds=data['proj_inds'], have=0, cur=[], batches=0, spheres=0, retries=0,
+                return dict(cloud=i, rng=rng, n=n, proj_inds=data['proj_inds'], proj_dev=getattr(data['search_tree'], 'proj_dev', None), have=0, cur=[], batches=0, spheres=0, retries=0,
                             check=False, points=data['search_tree']._pts().contiguous(), possibility=torch.from_numpy(poss).to(dev),
                             label=torch.from_numpy(np.ascontiguousarray(data['label'], dtype=np.int32)).to(dev), feat=feat)
             return None
@@ -938,7 +943,7 @@ class KPFCNN(nn.Module):
             t.buf.update(splits_dev=torch.from_numpy(t.splits).to(dev), cand=torch.empty(int(t.splits[-1]), dtype=torch.int32, device=dev))
             return t.buf
 
-        t = CloudSlots(S, admit_next, retired, dev, C_)
+        t = CloudSlots(S, admit_next, retired, dev, C_, k['finish'])
         slots = t.slots
         if not slots:
             return
@@ -960,6 +965,7 @@ class KPFCNN(nn.Module):
                 host = torch.cat([mins, cnt.to(torch.float64)]).cpu().numpy()          # the ONE read-back of the sub-round
                 stats['read_backs'] += 1
                 stats['sub_rounds'] += 1
+                t.poll()                                          # (retires whose copies have completed meanwhile)
                 mins_h, cnt_h = host[:nC], host[nC:].astype(np.int64)
                 # the finished test runs at a cloud's batch boundary only, like inference_end
                 finished = [s_ for s_ in need if slots[s_]['check'] and mins_h[s_] > 0.5]
@@ -1043,6 +1049,7 @@ class KPFCNN(nn.Module):
                 st.update(cur=[], have=0, batches=st['batches'] + 1, check=True)
             if on_batch is not None:
                 on_batch(spheres, batch, logits)
+        t.drain()
 
     def get_optimizer(self, cfg_pipeline):
         """kpconv.py:293-313: SGD with a separate learning rate for the deformable offsets' parameters."""

@@ -18,7 +18,7 @@ from ... import _abi
 from ... import ops
 from . import _randla_pack
 from ._datapath import GpuSearchTree, preprocess_segmentation   # noqa: F401
-from ._multicloud import CloudSlots, PinnedUpload, check_many_args
+from ._multicloud import CloudSlots, PinnedUpload, check_many_args, finish_cloud
 
 
 class SharedMLP(nn.Module):
@@ -483,6 +483,7 @@ class RandLANet(nn.Module):
         self.inference_ori_data = data
         self.inference_data = self.preprocess(data, attr)
         self.inference_proj_inds = self.inference_data['proj_inds']
+        self._inference_proj_dev = getattr(self.inference_data['search_tree'], 'proj_dev', None)
         num_points = self.inference_data['search_tree'].data.shape[0]
         self.possibility = self.rng.random(num_points) * 1e-3
         self.test_probs = torch.zeros((num_points, self.cfg.num_classes), dtype=torch.float16, device=self.device)
@@ -673,9 +674,8 @@ class RandLANet(nn.Module):
     def inference_end(self, inputs, results):
         self.update_probs(inputs, results, self.test_probs)
         if self._min_possibility() > 0.5:
-            probs = self.test_probs.cpu().numpy()
-            pred_labels = np.argmax(probs, 1)[self.inference_proj_inds]
-            self.inference_result = {'predict_labels': pred_labels, 'predict_scores': probs[self.inference_proj_inds]}
+            # np.argmax(probs, 1)[proj_inds] and probs[proj_inds] of the reference, taken on the device (ml3d_vote_project)
+            self.inference_result = finish_cloud(self.test_probs, self.inference_proj_inds, getattr(self, '_inference_proj_dev', None))
             return True
         return False
 
@@ -684,7 +684,7 @@ class RandLANet(nn.Module):
     # adding num_points floats in order) with a blocking read of the minimum possibility after every patch; the forward runs at
     # batch 1.  A cloud's patches depend only on its own possibilities and its own shuffle draws -- never on a logit -- so C clouds
     # can advance in lock step and each still produces exactly the patch sequence it produces alone (tests/test_emulated_multicloud.py).
-    def inference_many(self, clouds, seeds=None, max_in_flight=16, on_batch=None):
+    def inference_many(self, clouds, seeds=None, max_in_flight=16, on_batch=None, finish="device"):
         """Segment a list of raw clouds (dicts as ``inference_begin`` takes) with up to ``max_in_flight`` of them advancing in lock
         step: per round ONE argmin + ONE read-back of the minima (the finished test), one batched sampler call
         (``ops.device_patch_batch``), one neighbour pyramid over [A, k, 3], one forward at batch A and one vote update into a
@@ -697,11 +697,14 @@ class RandLANet(nn.Module):
         ``inputs`` the batch in the batcher's layout (device tensors), ``logits`` [A, k, classes].
         A cloud the device loop cannot serve (fewer points than ``num_points`` after preprocessing, an augmentation it does not
         know) runs through the single-cloud loop on its own afterwards, with its generator.
-        ``self.inference_many_info[i]`` keeps, per cloud, ``num_patches`` and its final ``possibility`` (numpy float64)."""
+        ``self.inference_many_info[i]`` keeps, per cloud, ``num_patches`` and its final ``possibility`` (numpy float64).
+        ``finish``: where a finished cloud's votes become its result.  ``"device"``: one ``ops.vote_project`` and copies on a copy
+        stream while the loop goes on; ``"host"``: a blocking read-back, ``np.argmax`` and two gathers on the host with the loop
+        standing still (the A/B baseline).  The results are equal."""
         cfg, dev = self.cfg, self.device
         n_clouds = len(clouds)
         S, seeds = check_many_args("RandLANet.inference_many", self, n_clouds, max_in_flight, seeds,
-                                   lambda n: [int(s) for s in self.rng.integers(0, 2 ** 63 - 1, size=n)])
+                                   lambda n: [int(s) for s in self.rng.integers(0, 2 ** 63 - 1, size=n)], finish)
         self.test_smooth = 0.95
         k, C_ = int(cfg.num_points), int(cfg.num_classes)
         results = [None] * n_clouds
@@ -719,7 +722,8 @@ class RandLANet(nn.Module):
                 if st is None:
                     host_path.append(i)
                     continue
-                st.update(cloud=i, rng=rng, proj_inds=data['proj_inds'], n=int(n), patches=0)
+                st.update(cloud=i, rng=rng, proj_inds=data['proj_inds'], proj_dev=getattr(data['search_tree'], 'proj_dev', None),
+                          n=int(n), patches=0)
                 return st
             return None
 
@@ -727,7 +731,7 @@ class RandLANet(nn.Module):
             results[st['cloud']] = result
             info[st['cloud']] = dict(num_patches=st['patches'], possibility=possibility)
 
-        t = CloudSlots(S, admit_next, retired, dev, C_)
+        t = CloudSlots(S, admit_next, retired, dev, C_, finish)
         slots = t.slots
         if slots:
             idx = torch.zeros(len(slots), dtype=torch.int32, device=dev)
@@ -737,6 +741,7 @@ class RandLANet(nn.Module):
         while active:
             ops.possibility_argmin(t.buf['possibility'], t.splits, active, out=(idx, mins))
             mins_host = mins.cpu().numpy()                           # the ONE read-back of the round
+            t.poll()                                                 # (retires whose copies have completed meanwhile)
             finished = [s_ for s_ in active if mins_host[s_] > 0.5]
             if finished:
                 rebuilt = t.replace_finished(finished)
@@ -762,6 +767,7 @@ class RandLANet(nn.Module):
             ops.vote_update(buf['votes'], row.reshape(-1), logits.reshape(-1, C_), self.test_smooth)
             if on_batch is not None:
                 on_batch([slots[s_]['cloud'] for s_ in active], inputs, logits)
+        t.drain()
         # what the device loop cannot serve: the single-cloud loop, cloud by cloud, each with its own generator
         keep_rng = self.rng
         try:

@@ -5,6 +5,10 @@ clouds fed one after another through ``inference_begin`` / ``inference_preproces
 (never best-of).  Prints one JSON line and, with ``--markdown FILE``, writes the table of profiles/kpconv_multicloud_bench.md.
 
     python tools/bench_kpconv_multicloud.py [--clouds 8] [--repeats 5] [--in-flight 1,4,8] [--small] [--half 7.0] [--markdown FILE]
+                                            [--finish device|host]
+
+``--finish``: the ``finish`` of every ``inference_many`` call (default: the model's own default) -- where a finished cloud's votes
+become its result; ``host`` is the blocking read-back + numpy finish kept as the A/B baseline (profiles/multicloud_finish_bench.md).
 
 Clouds: synthetic Toronto3D-shaped tiles (``synth_data.toronto3d_tile``) at the sizes of kpconv_toronto3d.yml (0.08 m grid, 4 m
 spheres, batches of 5 000 .. 10 000 points; ``--small``: the tests' sizes, 0.12 m grid, 1 m spheres, batches of 600 .. 800).
@@ -48,14 +52,15 @@ def sequential(model, clouds, seeds):
     return spheres, batches
 
 
-def many(model, clouds, seeds, in_flight):
+def many(model, clouds, seeds, in_flight, finish=None):
     count = [0, 0]
 
     def on_batch(spheres, batch, logits):
         count[0] += len(spheres)
         count[1] += 1
 
-    res = model.inference_many(clouds, seeds=seeds, max_in_flight=in_flight, on_batch=on_batch)
+    kw = {} if finish is None else {"finish": finish}
+    res = model.inference_many(clouds, seeds=seeds, max_in_flight=in_flight, on_batch=on_batch, **kw)
     torch.cuda.synchronize()
     assert all(r is not None for r in res)
     return count[0], count[1]
@@ -68,6 +73,7 @@ def main():
     ap.add_argument("--in-flight", default="1,4,8")
     ap.add_argument("--half", type=float, default=7.0)
     ap.add_argument("--markdown", default=None)
+    ap.add_argument("--finish", choices=("device", "host"), default=None)
     ap.add_argument("--small", action="store_true", help="0.12 m grid, 1 m spheres, batches of 600 .. 800 points (the tests' sizes)")
     args = ap.parse_args()
     from ml3d.torch.models.kpconv import KPFCNN
@@ -85,7 +91,7 @@ def main():
     modes = [("sequential", None)]
     if hasattr(KPFCNN, "inference_many"):
         modes += [("inference_many_%d" % int(f), int(f)) for f in args.in_flight.split(",")]
-    run = lambda f: sequential(model, clouds, seeds) if f is None else many(model, clouds, seeds, f)
+    run = lambda f: sequential(model, clouds, seeds) if f is None else many(model, clouds, seeds, f, args.finish)
     counts = {name: run(f) for name, f in modes}                        # warm-up: every mode once, untimed
     assert len({c[0] for c in counts.values()}) == 1, counts            # the same seeds cut the same spheres in every mode
     times = {name: [] for name, _ in modes}
@@ -101,7 +107,7 @@ def main():
                 extra[name] = dict(model.inference_many_stats)
     n = counts["sequential"][0]
     out = {"tool": "bench_kpconv_multicloud", "clouds": len(clouds), "spheres": n, "repeats": args.repeats,
-           "raw_points_total": int(sum(len(c["point"]) for c in clouds))}
+           "raw_points_total": int(sum(len(c["point"]) for c in clouds)), "finish": args.finish or "default"}
     for name, _ in modes:
         t = np.asarray(times[name])
         out[name] = {"s_median": float(np.median(t)), "s_min": float(t.min()), "s_max": float(t.max()),

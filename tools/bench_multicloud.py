@@ -4,7 +4,10 @@ through ``inference_begin`` / ``inference_preprocess`` / forward / ``inference_e
 warm-up pass of every mode, medians and the spread over the repeats (never best-of).  Prints one JSON line
 (``preprocess_only``: the preprocessing of the clouds alone, which every mode's time contains).
 
-    python tools/bench_multicloud.py [--clouds 16] [--repeats 7] [--in-flight 1,4,16]
+    python tools/bench_multicloud.py [--clouds 16] [--repeats 7] [--in-flight 1,4,16] [--finish device|host]
+
+``--finish``: the ``finish`` of every ``inference_many`` call (default: the model's own default) -- where a finished cloud's votes
+become its result; ``host`` is the blocking read-back + numpy finish kept as the A/B baseline (profiles/multicloud_finish_bench.md).
 
 Clouds: synthetic SemanticKITTI-sized sweeps (``synth_data.lidar_sweep``, the generator bench.py uses), the first ``--clouds``
 seeds from 5000 on whose 0.06 m sub-cloud keeps more than num_points = 45 056 points (a smaller one would take the host path and
@@ -67,13 +70,14 @@ def preprocess_only(model, clouds):
     return 0
 
 
-def many(model, clouds, seeds, in_flight):
+def many(model, clouds, seeds, in_flight, finish=None):
     count = [0]
 
     def on_batch(slots, inputs, logits):
         count[0] += len(slots)
 
-    res = model.inference_many(clouds, seeds=seeds, max_in_flight=in_flight, on_batch=on_batch)
+    kw = {} if finish is None else {"finish": finish}
+    res = model.inference_many(clouds, seeds=seeds, max_in_flight=in_flight, on_batch=on_batch, **kw)
     torch.cuda.synchronize()
     assert all(r is not None for r in res)
     return count[0]
@@ -92,6 +96,7 @@ def main():
     ap.add_argument("--clouds", type=int, default=16)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--in-flight", default="1,4,16")
+    ap.add_argument("--finish", choices=("device", "host"), default=None)
     args = ap.parse_args()
     from ml3d.torch.models import RandLANet
     cfg = dict(synth_weights.RANDLANET_SEMANTICKITTI_CFG, grid_size=0.06, augment={"recenter": {"dim": [0, 1]}})
@@ -105,7 +110,7 @@ def main():
     if hasattr(RandLANet, "inference_many"):
         modes += [("inference_many_%d" % int(f), int(f)) for f in args.in_flight.split(",")]
     run = lambda f: sequential(model, clouds, seeds) if f is None else \
-        (preprocess_only(model, clouds) if f == "pre" else many(model, clouds, seeds, f))
+        (preprocess_only(model, clouds) if f == "pre" else many(model, clouds, seeds, f, args.finish))
     patches = {name: run(f) for name, f in modes}                       # warm-up: every mode once, untimed
     assert len(set(patches.values())) == 1, patches                     # the same seeds cut the same patches in every mode
     modes.append(("preprocess_only", "pre"))                            # side measurement: the per-cloud share of every mode's time
@@ -121,7 +126,7 @@ def main():
     n = patches["sequential"]
     out = {"tool": "bench_multicloud", "clouds": len(clouds), "num_points": int(cfg["num_points"]), "patches": n,
            "sub_cloud_points_total": int(n_sub),
-           "hip_graphs": bool(getattr(model, "use_graphs", False)), "repeats": args.repeats}
+           "hip_graphs": bool(getattr(model, "use_graphs", False)), "repeats": args.repeats, "finish": args.finish or "default"}
     for name, _ in modes:
         out[name] = stats(times[name], n if name != "preprocess_only" else 0, len(clouds))
     print(json.dumps(out))
