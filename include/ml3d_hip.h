@@ -632,6 +632,41 @@ int ml3d_iou_3d(const float* boxes_a, const float* boxes_b, int64_t n, int64_t m
 /*   NULL pointers (but out_scores_f16), num_classes out of range and n_full   */
 /*   or n_sub >= 2^31 are invalid (-1, before any HIP call).                   */
 /*   One launch, no workspace, no atomics, deterministic.                      */
+/* ml3d_vote_confusion / ml3d_score_confusion: ground-truth scoring of a       */
+/*   finished cloud -- filter_valid_label + SemSegMetric.update of the          */
+/*   reference's run_test (semantic_segmentation.py:250-257,                    */
+/*   semseg_metric.py:95-126) with only a C x C integer matrix to read back.    */
+/*   Prediction: pred_i = the label ml3d_vote_project gives point i -- argmax   */
+/*   of votes[proj_inds[i]], or of votes[i] with proj_inds == NULL (identity:   */
+/*   n_full must equal n_sub) -- by the same device function, same rule         */
+/*   (exactly converted float32, FIRST maximum, NaN is the maximum and the      */
+/*   first NaN wins, +0 == -0).  ml3d_score_confusion: pred_i = argmax of the   */
+/*   float32 row scores[i * ld .. i * ld + num_classes), ld >= num_classes, by  */
+/*   ml3d_argmax_labels' rule (the same one).                                   */
+/*   Ground truth: g = gt_labels[i], the dataset's label value.  g outside      */
+/*   [0, lut_size): counts[2] += 1 and nothing else.  label_lut[g] < 0 (an      */
+/*   ignored label): counts[1] += 1.  Otherwise confusion[label_lut[g] *        */
+/*   num_classes + pred_i] += 1 and counts[0] += 1.  label_lut == NULL is the   */
+/*   identity over [0, num_classes).  A table entry >= num_classes is invalid:  */
+/*   the table is host knowledge and the host wrapper checks it; the device     */
+/*   counts such a point in counts[2] and never writes outside the matrix.      */
+/*   Row = truth, column = prediction: np.bincount(C * y_true + y_pred).        */
+/*   confusion int64 [C * C] and counts int64 [3] are ADDED to (zero them for   */
+/*   one cloud's matrix; leave them for a running sum over clouds).             */
+/*   out_labels (ml3d_vote_confusion, may be NULL): receives pred_i for EVERY   */
+/*   i, ignored or not -- the bytes ml3d_vote_project writes.                   */
+/*   Alignment: votes_f16 is only 2-byte aligned, as for ml3d_vote_project.     */
+/*   1 <= num_classes <= 256.  n_full == 0 (n == 0) returns 0 and launches      */
+/*   nothing.  Invalid (-1, before any HIP call): num_classes out of range,     */
+/*   n_full, n_sub or n >= 2^31 or negative, n_sub == 0 with n_full > 0,        */
+/*   proj_inds == NULL with n_full != n_sub, ld < num_classes, a label_lut      */
+/*   with lut_size <= 0, and NULL pointers except proj_inds, label_lut and      */
+/*   out_labels.                                                                */
+/*   One launch, no workspace, nothing read back.  The sums are integer         */
+/*   atomicAdds (per workgroup in LDS for num_classes <= 64, one 64-bit add per */
+/*   non-zero cell to the matrix; above that straight to the matrix): integer   */
+/*   addition does not depend on the order of arrival, so the result is         */
+/*   deterministic.  No float atomics.                                          */
 /* ------------------------------------------------------------------------- */
 size_t ml3d_nearest_to_center_workspace_bytes(int64_t n_points);
 
@@ -645,6 +680,16 @@ int ml3d_vote_update(const float* logits, const int32_t* point_inds, int64_t n, 
 int ml3d_vote_project(const void* votes_f16, int64_t n_sub, int num_classes,
                       const int32_t* proj_inds, int64_t n_full,
                       uint8_t* out_labels, void* out_scores_f16, void* stream);
+
+int ml3d_vote_confusion(const void* votes_f16, int64_t n_sub, int num_classes,
+                        const int32_t* proj_inds /* NULL: identity, n_full == n_sub */, int64_t n_full,
+                        const int32_t* gt_labels /* [n_full] */, const int32_t* label_lut, int lut_size,
+                        int64_t* confusion /* [C*C], ADDED to */, int64_t* counts /* [3], ADDED to */,
+                        uint8_t* out_labels /* [n_full] or NULL */, void* stream);
+
+int ml3d_score_confusion(const float* scores, int64_t ld, int64_t n, int num_classes,
+                         const int32_t* gt_labels, const int32_t* label_lut, int lut_size,
+                         int64_t* confusion, int64_t* counts, void* stream);
 
 /* ---- the patch loop of one cloud with NOTHING read back (ABI 5) ------------------------------- */
 /* The sampler + transform of a test cloud (semseg_spatially_regular.py:64-111,                    */

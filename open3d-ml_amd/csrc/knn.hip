@@ -750,6 +750,29 @@ __device__ __forceinline__ float vp_float(unsigned short bits) {
     return __half2float(h);                                     // exact
 }
 
+// the label of one float16 row: the first maximum of the exactly converted values, NaN counts as the maximum and the first NaN wins
+// (np.argmax); the ONE statement of the rule, shared by vote_project and vote_confusion
+__device__ __forceinline__ int vp_argmax(const unsigned short* __restrict__ row, int C) {
+    float best = vp_float(row[0]);
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = vp_float(row[c]);
+        if ((v > best || v != v) && !(best != best)) { best = v; arg = c; }
+    }
+    return arg;
+}
+
+// the same rule on a float32 row (torch.argmax): argmax_rows, argmax_rows_lds and score_confusion
+__device__ __forceinline__ int argmax_row(const float* __restrict__ row, int C) {
+    float best = row[0];
+    int arg = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = row[c];
+        if ((v > best || v != v) && !(best != best)) { best = v; arg = c; }
+    }
+    return arg;
+}
+
 __global__ void __launch_bounds__(VP_ROWS)
 vote_project(const unsigned short* __restrict__ votes, int C, const int32_t* __restrict__ proj, int64_t n_full,
              uint8_t* __restrict__ out_labels, unsigned short* __restrict__ out_scores) {
@@ -775,14 +798,7 @@ vote_project(const unsigned short* __restrict__ votes, int C, const int32_t* __r
         }
     }
     if ((int)threadIdx.x >= rows) return;
-    const unsigned short* row = votes + (int64_t)proj[r0 + threadIdx.x] * C;
-    float best = vp_float(row[0]);
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-        const float v = vp_float(row[c]);
-        if ((v > best || v != v) && !(best != best)) { best = v; arg = c; }
-    }
-    out_labels[r0 + threadIdx.x] = (uint8_t)arg;
+    out_labels[r0 + threadIdx.x] = (uint8_t)vp_argmax(votes + (int64_t)proj[r0 + threadIdx.x] * C, C);
 }
 
 // labels = argmax over the classes (first maximum, NaN counts as the maximum -- torch.argmax), one thread per point
@@ -790,14 +806,7 @@ __global__ void __launch_bounds__(256)
 argmax_rows(const float* __restrict__ scores, int64_t n, int C, uint8_t* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float* row = scores + i * C;
-    float best = row[0];
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-        const float v = row[c];
-        if ((v > best || v != v) && !(best != best)) { best = v; arg = c; }
-    }
-    out[i] = (uint8_t)arg;
+    out[i] = (uint8_t)argmax_row(scores + i * C, C);
 }
 
 // the same for C <= 32 with the 64 rows of a workgroup staged through LDS: the rows are contiguous in memory, so the workgroup reads
@@ -826,14 +835,89 @@ argmax_rows_lds(const float* __restrict__ scores, int64_t n, int C, uint8_t* __r
     for (int e = head + 4 * n4 + threadIdx.x; e < total; e += 64) tile[e] = src[e];
     __syncthreads();
     if ((int)threadIdx.x >= rows) return;
-    const float* row = tile + threadIdx.x * C;
-    float best = row[0];
-    int arg = 0;
-    for (int c = 1; c < C; ++c) {
-        const float v = row[c];
-        if ((v > best || v != v) && !(best != best)) { best = v; arg = c; }
+    out[r0 + threadIdx.x] = (uint8_t)argmax_row(tile + threadIdx.x * C, C);
+}
+
+// ground-truth scoring of a finished cloud: confusion[lut[gt[i]] * C + pred_i] += 1 over the points of the FULL cloud, pred_i the
+// label vote_project gives point i (VOTES: vp_argmax of votes[proj[i]]; else argmax_row of scores[i]).  A workgroup owns VC_SHARE
+// consecutive points, one per thread and pass.  A real matrix puts most points on a handful of diagonal cells, so the sums are
+// taken per workgroup first: for C <= VC_LDS_CLASSES in a uint32 [C * C] table in LDS (a workgroup adds at most VC_SHARE), flushed
+// with ONE 64-bit atomicAdd per non-zero cell; above that straight into the matrix.  Integer sums: the result does not depend on
+// the order of arrival.  The three counters go the same way.  No lane leaves before the last barrier.
+constexpr int VC_THREADS = 256;
+constexpr int VC_SHARE = 4 * VC_THREADS;
+constexpr int VC_LDS_CLASSES = 64;                               // 64 * 64 * 4 = 16 KB of LDS
+constexpr int VC_LUT_LDS = 256;                                  // a LUT of up to 256 entries is staged in LDS
+
+#ifndef ML3D_CONFUSION_WAVE_MERGE
+// A/B switch (build time).  1: a wave merges its equal cells first -- a ballot over the leader's cell, one add of the lane count
+// per distinct cell -- before it touches the table; 0: every lane adds its own 1.  Default 0, the faster of the two on sweep-sized
+// clouds: profiles/multicloud_eval_bench.md has both times.
+#define ML3D_CONFUSION_WAVE_MERGE 0
+#endif
+
+template <bool VOTES>
+__global__ void __launch_bounds__(VC_THREADS)
+confusion_rows(const void* __restrict__ src, int64_t ld, int C, const int32_t* __restrict__ proj, int64_t n,
+               const int32_t* __restrict__ gt, const int32_t* __restrict__ lut, int lut_size,
+               unsigned long long* __restrict__ confusion, unsigned long long* __restrict__ counts, uint8_t* __restrict__ out_labels) {
+    __shared__ uint32_t tab[VC_LDS_CLASSES * VC_LDS_CLASSES];
+    __shared__ int32_t slut[VC_LUT_LDS];
+    __shared__ uint32_t cnt[3];
+    const bool in_lds = C <= VC_LDS_CLASSES;
+    const bool lut_lds = lut != nullptr && lut_size <= VC_LUT_LDS;
+    const int cells = C * C;
+    if (in_lds)
+        for (int c = threadIdx.x; c < cells; c += VC_THREADS) tab[c] = 0u;
+    if (lut_lds)
+        for (int c = threadIdx.x; c < lut_size; c += VC_THREADS) slut[c] = lut[c];
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const int range = lut ? lut_size : C;                        // the ground-truth values the table knows
+    const int64_t r0 = (int64_t)blockIdx.x * VC_SHARE;
+    for (int pass = 0; pass < VC_SHARE / VC_THREADS; ++pass) {
+        const int64_t i = r0 + pass * VC_THREADS + threadIdx.x;
+        int cell = -1;
+        if (i < n) {
+            int pred;
+            if (VOTES)
+                pred = vp_argmax(static_cast<const unsigned short*>(src) + (proj ? (int64_t)proj[i] : i) * ld, C);
+            else
+                pred = argmax_row(static_cast<const float*>(src) + i * ld, C);
+            if (out_labels) out_labels[i] = (uint8_t)pred;
+            const int g = gt[i];
+            int which = 2;                                       // outside the table (or a table entry outside the matrix)
+            if (g >= 0 && g < range) {
+                const int t = lut ? (lut_lds ? slut[g] : lut[g]) : g;
+                if (t < 0) which = 1;                            // ignored
+                else if (t < C) { which = 0; cell = t * C + pred; }
+            }
+            atomicAdd(&cnt[which], 1u);
+        }
+#if ML3D_CONFUSION_WAVE_MERGE
+        unsigned long long todo = __ballot(cell >= 0);           // (wave-uniform from here: every lane takes every turn)
+        while (todo) {
+            const int leader = __ffsll(todo) - 1;
+            const int lead_cell = __shfl(cell, leader);
+            const unsigned long long same = __ballot(cell == lead_cell);
+            if ((int)(threadIdx.x & 63) == leader) {
+                if (in_lds) atomicAdd(&tab[lead_cell], (uint32_t)__popcll(same));
+                else atomicAdd(&confusion[lead_cell], (unsigned long long)__popcll(same));
+            }
+            todo &= ~same;
+        }
+#else
+        if (cell >= 0) {
+            if (in_lds) atomicAdd(&tab[cell], 1u);
+            else atomicAdd(&confusion[cell], 1ull);
+        }
+#endif
     }
-    out[r0 + threadIdx.x] = (uint8_t)arg;
+    __syncthreads();
+    if (in_lds)
+        for (int c = threadIdx.x; c < cells; c += VC_THREADS)
+            if (tab[c]) atomicAdd(&confusion[c], (unsigned long long)tab[c]);
+    if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
 }
 
 }  // namespace ml3d
@@ -1011,5 +1095,31 @@ extern "C" int ml3d_vote_project(const void* votes_f16, int64_t n_sub, int num_c
     if (n_sub == 0 || !votes_f16 || !proj_inds || !out_labels) return ML3D_E_INVALID;
     hipLaunchKernelGGL(vote_project, dim3((unsigned)((n_full + VP_ROWS - 1) / VP_ROWS)), dim3(VP_ROWS), 0, (hipStream_t)stream,
                        (const unsigned short*)votes_f16, num_classes, proj_inds, n_full, out_labels, (unsigned short*)out_scores_f16);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" int ml3d_vote_confusion(const void* votes_f16, int64_t n_sub, int num_classes, const int32_t* proj_inds, int64_t n_full,
+                                   const int32_t* gt_labels, const int32_t* label_lut, int lut_size, int64_t* confusion, int64_t* counts,
+                                   uint8_t* out_labels, void* stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_full < 0 || n_sub < 0 || n_full >= lim || n_sub >= lim || num_classes <= 0 || num_classes > 256) return ML3D_E_INVALID;
+    if ((label_lut && lut_size <= 0) || (!proj_inds && n_full != n_sub)) return ML3D_E_INVALID;
+    if (n_full == 0) return 0;
+    if (n_sub == 0 || !votes_f16 || !gt_labels || !confusion || !counts) return ML3D_E_INVALID;
+    hipLaunchKernelGGL(confusion_rows<true>, dim3((unsigned)((n_full + VC_SHARE - 1) / VC_SHARE)), dim3(VC_THREADS), 0, (hipStream_t)stream,
+                       votes_f16, (int64_t)num_classes, num_classes, proj_inds, n_full, gt_labels, label_lut, lut_size,
+                       (unsigned long long*)confusion, (unsigned long long*)counts, out_labels);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" int ml3d_score_confusion(const float* scores, int64_t ld, int64_t n, int num_classes, const int32_t* gt_labels,
+                                    const int32_t* label_lut, int lut_size, int64_t* confusion, int64_t* counts, void* stream) {
+    if (n < 0 || n >= ((int64_t)1 << 31) || num_classes <= 0 || num_classes > 256 || ld < num_classes) return ML3D_E_INVALID;
+    if (label_lut && lut_size <= 0) return ML3D_E_INVALID;
+    if (n == 0) return 0;
+    if (!scores || !gt_labels || !confusion || !counts) return ML3D_E_INVALID;
+    hipLaunchKernelGGL(confusion_rows<false>, dim3((unsigned)((n + VC_SHARE - 1) / VC_SHARE)), dim3(VC_THREADS), 0, (hipStream_t)stream,
+                       (const void*)scores, ld, num_classes, (const int32_t*)nullptr, n, gt_labels, label_lut, lut_size,
+                       (unsigned long long*)confusion, (unsigned long long*)counts, (uint8_t*)nullptr);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

@@ -75,7 +75,7 @@ SYMBOLS = [
     "ml3d_patch_recenter",
     "ml3d_possibility_argmin_workspace_bytes", "ml3d_possibility_argmin", "ml3d_patch_batch_workspace_bytes", "ml3d_patch_batch",
     "ml3d_sphere_select_workspace_bytes", "ml3d_sphere_select", "ml3d_sphere_batch_workspace_bytes", "ml3d_sphere_batch",
-    "ml3d_vote_update", "ml3d_vote_project",
+    "ml3d_vote_update", "ml3d_vote_project", "ml3d_vote_confusion", "ml3d_score_confusion",
     "ml3d_randla_gather_max",
     "ml3d_randla_gather_max_backward",
     "ml3d_randla_attentive_pool",
@@ -358,6 +358,10 @@ def bind(lib):
     lib.ml3d_vote_update.argtypes = [vp, vp, i64, i32, f32, vp, i64, vp]
     lib.ml3d_vote_project.restype = C.c_int
     lib.ml3d_vote_project.argtypes = [vp, i64, i32, vp, i64, vp, vp, vp]
+    lib.ml3d_vote_confusion.restype = C.c_int
+    lib.ml3d_vote_confusion.argtypes = [vp, i64, i32, vp, i64, vp, vp, i32, vp, vp, vp, vp]
+    lib.ml3d_score_confusion.restype = C.c_int
+    lib.ml3d_score_confusion.argtypes = [vp, i64, i64, i32, vp, vp, i32, vp, vp, vp]
     lib.ml3d_argmax_labels.restype = C.c_int
     lib.ml3d_argmax_labels.argtypes = [vp, i64, i32, vp, vp]
     lib.ml3d_randla_pyramid_workspace_bytes.restype = sz

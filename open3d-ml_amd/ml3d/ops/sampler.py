@@ -369,3 +369,133 @@ def vote_project(votes, proj_inds, out_labels=None, out_scores=None, scores=True
                                    None if out_scores is None else out_scores.data_ptr(), _stream())
     _abi.check(rc, "ml3d_vote_project")
     return out_labels, out_scores
+
+
+def label_lut(num_classes, ignored_label_inds):
+    """HOST int32 table from a dataset's label VALUE to its row of the confusion matrix, -1 for an ignored value: the table
+    ``valid_scores_and_labels`` builds (modules/losses.py:78-85 -- an identity over ``num_classes`` with a zero inserted at every
+    ignored index >= 0, in LIST order) with every entry whose index is an ignored value set to -1 afterwards (the points the
+    reference drops before it looks the others up).  Length ``num_classes`` + the number of ignored indices >= 0."""
+    table = list(range(int(num_classes)))
+    ign = [int(i) for i in ignored_label_inds]
+    for i in ign:
+        if i >= 0:
+            table = table[:i] + [0] + table[i:]
+    for i in ign:
+        if 0 <= i < len(table):
+            table[i] = -1
+    return np.asarray(table, dtype=np.int32)
+
+
+def _confusion_args(what, num_classes, n, gt_labels, lut, confusion, counts, dev):
+    """The checks and allocations the two confusion ops share, before any device scope.  Returns (HOST lut or None, DEVICE lut or
+    None, confusion int64 [C, C], counts int64 [3])."""
+    C_ = int(num_classes)
+    if gt_labels.dtype != torch.int32 or gt_labels.dim() != 1 or not gt_labels.is_contiguous() or gt_labels.numel() != n:
+        raise RuntimeError("%s: invalid argument: gt_labels must be a contiguous int32 [n_full] tensor, one entry per point" % what)
+    if n >= 2 ** 31:
+        raise RuntimeError("%s: invalid argument: at most 2^31 - 1 points" % what)
+    lut_host = lut_dev = None
+    if isinstance(lut, torch.Tensor) and lut.device.type != "cpu":
+        # a table already on the device (the multi-cloud loops upload theirs once) is NOT read back: its shape is checked here, its
+        # values by whoever built it -- the kernel counts an entry >= classes in counts[2] and never writes outside the matrix
+        if lut.dtype != torch.int32 or lut.dim() != 1 or lut.numel() < 1 or not lut.is_contiguous() or lut.device != dev:
+            raise RuntimeError("%s: invalid argument: a device lut must be a non-empty contiguous int32 [lut_size] tensor on the "
+                               "votes' device" % what)
+        lut_dev = lut
+    elif lut is not None:
+        lut_host = np.ascontiguousarray(lut.detach().numpy() if isinstance(lut, torch.Tensor) else lut)
+        if lut_host.ndim != 1 or lut_host.size < 1 or lut_host.dtype.kind not in "iu" or int(lut_host.max()) >= C_:
+            raise RuntimeError("%s: invalid argument: lut must be a non-empty 1-d integer table with every entry < num_classes "
+                               "(negative: ignored)" % what)
+        lut_host = lut_host.astype(np.int32)
+        lut_dev = torch.from_numpy(lut_host).to(dev)
+    if confusion is None:
+        confusion = torch.zeros((C_, C_), dtype=torch.int64, device=dev)
+    elif confusion.dtype != torch.int64 or tuple(confusion.shape) != (C_, C_) or not confusion.is_contiguous():
+        raise RuntimeError("%s: invalid argument: confusion must be a contiguous int64 [classes, classes] tensor" % what)
+    if counts is None:
+        counts = torch.zeros(3, dtype=torch.int64, device=dev)
+    elif counts.dtype != torch.int64 or tuple(counts.shape) != (3,) or not counts.is_contiguous():
+        raise RuntimeError("%s: invalid argument: counts must be a contiguous int64 [3] tensor" % what)
+    _need_gpu(gt_labels, confusion, counts)
+    if gt_labels.device != dev or confusion.device != dev or counts.device != dev:
+        raise RuntimeError("%s: invalid argument: gt_labels, confusion and counts must be on the device of the votes / scores" % what)
+    return lut_host, lut_dev, confusion, counts
+
+
+def vote_confusion(votes, proj_inds, gt_labels, lut=None, confusion=None, counts=None, labels=False):
+    """Ground-truth scoring of a finished cloud on the device: filter_valid_label + SemSegMetric.update of the reference's
+    ``run_test`` (semantic_segmentation.py:250-257), one launch (``ml3d_vote_confusion``), integer atomics only, deterministic.
+
+    * Prediction: ``pred = np.argmax(votes, 1)[proj_inds]`` -- ``vote_project``'s labels, by the same device function.
+      ``proj_inds=None`` is the identity (n_full == n_sub).
+    * Ground truth: ``g = gt_labels[i]`` (int32 [n_full], the dataset's label VALUES, on the votes' device).  ``lut[g] >= 0``:
+      ``confusion[lut[g], pred] += 1`` and ``counts[0] += 1``.  ``lut[g] < 0`` (ignored): ``counts[1] += 1``.  ``g`` outside the
+      table: ``counts[2] += 1``.
+    * ``lut``: ``label_lut``'s table as a host array or CPU tensor (every entry < classes, checked), or an int32 tensor already on
+      the votes' device, which is used as it is without a read-back of its values.  None: the identity over the classes.
+    * ``confusion`` int64 [C, C] (row = truth, column = prediction) and ``counts`` int64 [3], on the votes' device: allocated
+      zeroed when None, else ADDED to.
+    * ``labels``: True, or the uint8 [n_full] tensor to write: ``pred`` for every point, ignored or not.
+
+    Returns ``(confusion, counts)``, or ``(confusion, counts, labels)`` when labels were asked for."""
+    lib = _abi.get()
+    _need_gpu(votes, gt_labels)
+    if votes.dtype != torch.float16 or votes.dim() != 2 or not votes.is_contiguous() or not (1 <= votes.shape[1] <= 256):
+        raise RuntimeError("vote_confusion: invalid argument: votes must be a contiguous float16 [n_sub, classes] tensor with "
+                           "1 <= classes <= 256")
+    n_sub, C_ = int(votes.shape[0]), int(votes.shape[1])
+    if proj_inds is None:
+        n_full = n_sub
+    else:
+        _need_gpu(proj_inds)
+        if proj_inds.dtype != torch.int32 or proj_inds.dim() != 1 or not proj_inds.is_contiguous():
+            raise RuntimeError("vote_confusion: invalid argument: proj_inds must be a contiguous int32 [n_full] tensor (or None)")
+        n_full = int(proj_inds.numel())
+        if n_full and not n_sub:
+            raise RuntimeError("vote_confusion: invalid argument: no votes to project")
+        if proj_inds.device != votes.device:
+            raise RuntimeError("vote_confusion: invalid argument: proj_inds must be on the votes' device")
+    dev = votes.device
+    _, lut_dev, confusion, counts = _confusion_args("vote_confusion", C_, n_full, gt_labels, lut, confusion, counts, dev)
+    out_labels = None
+    if isinstance(labels, torch.Tensor):
+        out_labels = labels
+        if out_labels.dtype != torch.uint8 or out_labels.numel() != n_full or not out_labels.is_contiguous():
+            raise RuntimeError("vote_confusion: invalid argument: labels must be a contiguous uint8 tensor with one entry per point")
+        _need_gpu(out_labels)
+        if out_labels.device != dev:
+            raise RuntimeError("vote_confusion: invalid argument: labels must be on the votes' device")
+    elif labels:
+        out_labels = torch.empty(n_full, dtype=torch.uint8, device=dev)
+    if n_full == 0:                             # (an empty tensor's address is NULL, which the library reads as "no projection")
+        return (confusion, counts) if out_labels is None else (confusion, counts, out_labels)
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_vote_confusion(votes.data_ptr(), n_sub, C_, None if proj_inds is None else proj_inds.data_ptr(), n_full,
+                                     gt_labels.data_ptr(), None if lut_dev is None else lut_dev.data_ptr(),
+                                     0 if lut_dev is None else int(lut_dev.numel()), confusion.data_ptr(), counts.data_ptr(),
+                                     None if out_labels is None else out_labels.data_ptr(), _stream())
+    _abi.check(rc, "ml3d_vote_confusion")
+    return (confusion, counts) if out_labels is None else (confusion, counts, out_labels)
+
+
+def score_confusion(scores, gt_labels, lut=None, confusion=None, counts=None):
+    """``vote_confusion`` for float32 ``scores`` [n, C <= 256] (rows may be a column slice of a wider contiguous matrix: row pitch
+    ``scores.stride(0)`` >= C, unit column stride): ``pred = argmax`` by ``argmax_labels``' rule.  What ``SemSegMetric.update``
+    does with device tensors.  Returns ``(confusion, counts)``."""
+    lib = _abi.get()
+    _need_gpu(scores, gt_labels)
+    if scores.dtype != torch.float32 or scores.dim() != 2 or not (1 <= scores.shape[1] <= 256):
+        raise RuntimeError("score_confusion: invalid argument: scores must be a float32 [n, classes] tensor with 1 <= classes <= 256")
+    n, C_ = int(scores.shape[0]), int(scores.shape[1])
+    ld = C_ if n <= 1 else int(scores.stride(0))
+    if (C_ > 1 and scores.stride(1) != 1) or ld < C_:
+        raise RuntimeError("score_confusion: invalid argument: scores rows must be contiguous (unit column stride, row pitch >= classes)")
+    dev = scores.device
+    _, lut_dev, confusion, counts = _confusion_args("score_confusion", C_, n, gt_labels, lut, confusion, counts, dev)
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_score_confusion(scores.data_ptr(), ld, n, C_, gt_labels.data_ptr(), None if lut_dev is None else lut_dev.data_ptr(),
+                                      0 if lut_dev is None else int(lut_dev.numel()), confusion.data_ptr(), counts.data_ptr(), _stream())
+    _abi.check(rc, "ml3d_score_confusion")
+    return confusion, counts

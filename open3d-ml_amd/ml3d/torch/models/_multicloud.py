@@ -29,6 +29,37 @@ def check_many_args(name, model, n_clouds, max_in_flight, seeds, draw_seeds, fin
     return S, seeds
 
 
+def eval_labels(name, clouds, evaluate):
+    """``evaluate=True``: per cloud its ground-truth labels of the FULL cloud (the dataset's label values, int32 [len(point)]) or None
+    where the dict carries no ``label``; a length mismatch is a ``ValueError`` here, before any patch runs.  Otherwise all None."""
+    out = [None] * len(clouds)
+    if not evaluate:
+        return out
+    for i, c in enumerate(clouds):
+        lab = c.get('label', None)
+        if lab is None:
+            continue
+        lab = np.ascontiguousarray(np.asarray(lab).reshape(-1), dtype=np.int32)
+        if lab.size != len(c['point']):
+            raise ValueError("%s: cloud %d has %d points and %d labels (evaluate=True scores the FULL cloud)" % (name, i, len(c['point']), lab.size))
+        out[i] = lab
+    return out
+
+
+def new_metric():
+    """An empty ``SemSegMetric`` (imported here: ``..modules`` imports model code)."""
+    from ..modules.metrics import SemSegMetric
+    return SemSegMetric()
+
+
+def score_on_host(result, gt, lut, num_classes):
+    """Add ``'confusion'`` and ``'counts'`` of ``result['predict_labels']`` against ``gt`` to a cloud's result (None: not scored)."""
+    if gt is not None:
+        from ..modules.metrics import host_confusion          # (imported here, like new_metric)
+        result['confusion'], result['counts'] = host_confusion(result['predict_labels'], gt, lut, num_classes)
+    return result
+
+
 def finish_cloud(votes, proj_inds, proj_dev=None):
     """The finish of the single-cloud loops (``inference_end``), synchronous: the float16 device ``votes`` through ``proj_inds`` by
     ``ops.vote_project`` -> ``{'predict_labels': int64, 'predict_scores': float16}``, the arrays ``np.argmax(probs, 1)[proj_inds]`` and
@@ -52,12 +83,23 @@ class CloudSlots:
     ``finish='device'``: a finished cloud's votes are projected by ``ops.vote_project`` and copied out on a copy stream, and
     ``retired`` is called from ``poll()`` -- the loop calls it where it reads back its minima -- or ``drain()`` -- before the loop
     returns -- once the copies have completed; the state may carry ``proj_dev``, the device copy of ``proj_inds`` (int32).
-    ``finish='host'``: ``retired`` is called from within ``replace_finished``."""
+    ``finish='host'``: ``retired`` is called from within ``replace_finished``.
+    ``evaluate``: a state that carries ``gt`` (int32 numpy [n_full], the full cloud's label values) is scored against the HOST table
+    ``lut`` (``ops.label_lut``): its result gains ``'confusion'`` (int64 [C, C]) and ``'counts'`` (int64 [3]).  The labels go up once,
+    at admission (``gt_dev``); ``finish='device'`` scores by ``ops.vote_confusion`` and the matrix rides the labels' staging set and
+    event, ``finish='host'`` by numpy (``modules.metrics.host_confusion``).  ``return_scores=False``: ``'predict_scores'`` is None -- no score rows are
+    written, staged or copied.  With both at their defaults nothing differs from a table without them."""
     ARRAYS = ('points', 'possibility', 'label', 'votes')
 
-    def __init__(self, max_in_flight, admit, retired, device, num_classes, finish="host"):
+    def __init__(self, max_in_flight, admit, retired, device, num_classes, finish="host", evaluate=False, return_scores=True, lut=None):
         self._admit, self._retired, self.device, self.num_classes = admit, retired, device, int(num_classes)
         self.finish = finish
+        self.evaluate, self.return_scores = bool(evaluate), bool(return_scores)
+        self.lut = self.lut_dev = None
+        if self.evaluate:
+            self.lut = np.arange(self.num_classes, dtype=np.int32) if lut is None else np.ascontiguousarray(lut, dtype=np.int32)
+            if finish == "device":
+                self.lut_dev = torch.from_numpy(self.lut).to(device)
         self._copy = None                      # the ONE extra stream, made by the first device retire
         self._pending, self._free = [], []     # retires on their way out, oldest first; staging buffers whose copies have completed
         self.slots, self.buf, self.splits = [], {}, np.zeros(1, np.int64)
@@ -73,6 +115,8 @@ class CloudSlots:
         st = self._admit()
         if st is not None:
             st['votes'] = torch.zeros((st['n'], self.num_classes), dtype=torch.float16, device=self.device)
+            if self.evaluate and self.finish == "device" and st.get('gt') is not None:
+                st['gt_dev'] = torch.from_numpy(st['gt']).to(self.device)          # once per cloud, next to proj_dev
         return st
 
     def active(self):
@@ -109,20 +153,28 @@ class CloudSlots:
         st = self.slots[slot]
         a, b = self.rows(slot)
         probs = self.buf['votes'][a:b].cpu().numpy()
-        result = {'predict_labels': np.argmax(probs, 1)[st['proj_inds']], 'predict_scores': probs[st['proj_inds']]}
+        result = {'predict_labels': np.argmax(probs, 1)[st['proj_inds']],
+                  'predict_scores': probs[st['proj_inds']] if self.return_scores else None}
+        if self.evaluate:
+            score_on_host(result, st.get('gt'), self.lut, self.num_classes)
         self.slots[slot] = None
         return st, result, self.buf['possibility'][a:b].cpu().numpy()
 
     def _staging(self, n_full, n_sub):
         """Pinned host buffers for one retire (device-to-host copies go through pinned memory, like ``PinnedUpload``'s uploads): a
-        set from ``_free`` -- sets whose copies' event HAS completed, no other is ever handed out again -- or a new one."""
+        set from ``_free`` -- sets whose copies' event HAS completed, no other is ever handed out again -- or a new one.  A set has
+        room for the scores only with ``return_scores`` and for a matrix and its counts only with ``evaluate``."""
         for i, sg in enumerate(self._free):
             if sg['labels'].numel() >= n_full and sg['possibility'].numel() >= n_sub:
                 return self._free.pop(i)
         room = lambda n: 1 << int(max(n, 1) - 1).bit_length()
-        return dict(labels=torch.empty(room(n_full), dtype=torch.uint8).pin_memory(),
-                    scores=torch.empty(room(n_full) * self.num_classes, dtype=torch.float16).pin_memory(),
-                    possibility=torch.empty(room(n_sub), dtype=torch.float64).pin_memory())
+        sg = dict(labels=torch.empty(room(n_full), dtype=torch.uint8).pin_memory(),
+                  possibility=torch.empty(room(n_sub), dtype=torch.float64).pin_memory())
+        if self.return_scores:
+            sg['scores'] = torch.empty(room(n_full) * self.num_classes, dtype=torch.float16).pin_memory()
+        if self.evaluate:
+            sg['eval'] = torch.empty(self.num_classes * self.num_classes + 3, dtype=torch.int64).pin_memory()
+        return sg
 
     def retire_async(self, slot):
         """The ``finish='device'`` route.  Empty ``slot`` without stopping the loop: one ``ops.vote_project`` over the cloud's rows on
@@ -135,7 +187,18 @@ class CloudSlots:
             proj = torch.from_numpy(np.ascontiguousarray(st['proj_inds'], dtype=np.int32).reshape(-1)).to(self.device)
         votes, poss = self.buf['votes'][a:b], self.buf['possibility'][a:b]
         n_full, n_sub, C_ = int(proj.numel()), b - a, self.num_classes
-        labels, scores = ops.vote_project(votes, proj)
+        gt = st.get('gt_dev') if self.evaluate else None
+        ev = scores = None
+        if gt is not None:                      # the matrix and its three counts in ONE tensor: one zero fill, one copy
+            ev = torch.zeros(C_ * C_ + 3, dtype=torch.int64, device=self.device)
+        if self.return_scores:
+            labels, scores = ops.vote_project(votes, proj)
+            if gt is not None:
+                ops.vote_confusion(votes, proj, gt, self.lut_dev, confusion=ev[:C_ * C_].view(C_, C_), counts=ev[C_ * C_:])
+        elif gt is not None:                    # labels-only evaluation: one launch
+            labels = ops.vote_confusion(votes, proj, gt, self.lut_dev, confusion=ev[:C_ * C_].view(C_, C_), counts=ev[C_ * C_:], labels=True)[2]
+        else:
+            labels, _ = ops.vote_project(votes, proj, scores=False)
         ready = torch.cuda.Event()
         ready.record()                          # behind the projection and every round that wrote these possibilities
         if self._copy is None:
@@ -144,7 +207,10 @@ class CloudSlots:
         with torch.cuda.stream(self._copy):
             self._copy.wait_event(ready)
             sg['labels'][:n_full].copy_(labels, non_blocking=True)
-            sg['scores'][:n_full * C_].copy_(scores.reshape(-1), non_blocking=True)
+            if scores is not None:
+                sg['scores'][:n_full * C_].copy_(scores.reshape(-1), non_blocking=True)
+            if ev is not None:
+                sg['eval'].copy_(ev, non_blocking=True)
             sg['possibility'][:n_sub].copy_(poss, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self._copy)
@@ -154,16 +220,21 @@ class CloudSlots:
         # ``poss`` view (hence the old possibility buffer) referenced until ``done`` has completed, so nothing is freed early.
         # ``record_stream`` as well, for the one case in which the entry does not live that long: a loop left by an exception
         # (``on_batch`` may raise) drops the table with copies on their way.
-        for src in (labels, scores, poss):
-            src.record_stream(self._copy)
-        self._pending.append(dict(done=done, state=st, staging=sg, n_full=n_full, n_sub=n_sub, keep=(labels, scores, poss, proj)))
+        for src in (labels, scores, poss, ev):
+            if src is not None:
+                src.record_stream(self._copy)
+        self._pending.append(dict(done=done, state=st, staging=sg, n_full=n_full, n_sub=n_sub, scored=ev is not None,
+                                  keep=(labels, scores, poss, proj, ev, gt)))
 
     def _deliver(self, p):
         """``p['done']`` has completed: copy the arrays out of the staging buffers (the results OWN their memory; the buffers go
         back to ``_free``, and only now) and hand them to ``retired``."""
         sg, n_full, n_sub, C_ = p['staging'], p['n_full'], p['n_sub'], self.num_classes
         result = {'predict_labels': sg['labels'][:n_full].numpy().astype(np.int64),              # (astype copies)
-                  'predict_scores': sg['scores'][:n_full * C_].numpy().reshape(n_full, C_).copy()}
+                  'predict_scores': sg['scores'][:n_full * C_].numpy().reshape(n_full, C_).copy() if self.return_scores else None}
+        if p['scored']:
+            both = sg['eval'].numpy().copy()
+            result['confusion'], result['counts'] = both[:C_ * C_].reshape(C_, C_).copy(), both[C_ * C_:].copy()
         possibility = sg['possibility'][:n_sub].numpy().copy()
         p['keep'] = None
         self._free.append(sg)

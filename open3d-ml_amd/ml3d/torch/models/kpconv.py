@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from ... import _abi
 from ... import ops
-from ._multicloud import CloudSlots, PinnedUpload, check_many_args, finish_cloud
+from ._multicloud import CloudSlots, PinnedUpload, check_many_args, eval_labels, finish_cloud, new_metric, score_on_host
 
 
 class _Cfg(dict):
@@ -848,7 +848,7 @@ class KPFCNN(nn.Module):
         finally:
             np.random.set_state(state)
 
-    def inference_many(self, clouds, seeds=None, max_in_flight=8, on_batch=None, finish="host"):
+    def inference_many(self, clouds, seeds=None, max_in_flight=8, on_batch=None, finish="host", evaluate=False, return_scores=True):
         """Segment a list of raw clouds (dicts as ``inference_begin`` takes) with up to ``max_in_flight`` of them advancing in lock
         step.  One SUB-ROUND cuts the next input sphere of every cloud whose batch is not complete: one ``ops.possibility_argmin``,
         one ``ops.sphere_select``, ONE read-back (the sphere sizes and, for clouds at a batch boundary, the minima of the finished
@@ -870,7 +870,14 @@ class KPFCNN(nn.Module):
         on the host with the loop standing still; ``"device"``: one ``ops.vote_project`` and copies on a copy stream while the loop
         goes on.  The results are equal.  The default is ``"host"``: on this loop's measured workload (tiles of ~25 000 raw points)
         the device route's medians lay inside the spread of the host route's and of the parent revision's runs
-        (profiles/multicloud_finish_bench.md), unlike RandLA-Net's, whose default is ``"device"``."""
+        (profiles/multicloud_finish_bench.md), unlike RandLA-Net's, whose default is ``"device"``.
+        ``evaluate=True``: a cloud whose dict carries ``label`` -- the dataset's label values of the FULL cloud, one per raw point (a
+        wrong length is a ``ValueError`` before any sphere is cut) -- is scored against it as the reference's ``run_test`` does
+        (filter_valid_label + SemSegMetric.update, with ``cfg.num_classes`` and ``cfg.ignored_label_inds``): its result gains
+        ``'confusion'`` (int64 [C, C], row = truth) and ``'counts'`` (int64 [3]: scored, ignored, outside the label table), and
+        ``self.inference_many_metric`` is a ``SemSegMetric`` holding the sum over the scored clouds.  ``finish="device"`` scores by
+        ``ops.vote_confusion`` with only the matrix copied out, ``finish="host"`` and the single-cloud loop by numpy: same numbers.
+        ``return_scores=False``: ``'predict_scores'`` is None and no score row is written or copied."""
         import time
         cfg, n_clouds = self.cfg, len(clouds)
         S, seeds = check_many_args("KPFCNN.inference_many", self, n_clouds, max_in_flight, seeds,
@@ -883,6 +890,9 @@ class KPFCNN(nn.Module):
         sampler = getattr(self, 'trans_point_sampler', None)
         host_only = cfg.get('sampler_index', 'gpu') == 'sklearn' or (sampler is not None and sampler != self._possibility_sampler) or \
             (linear and norm.get('normalize_points', False))
+        gts = eval_labels("KPFCNN.inference_many", clouds, evaluate)
+        lut = ops.label_lut(cfg.num_classes, cfg.get('ignored_label_inds', []) or []) if evaluate else None
+        metric = self.inference_many_metric = new_metric() if evaluate else None
         results = [None] * n_clouds
         info = self.inference_many_info = [None] * n_clouds
         stats = self.inference_many_stats = dict(read_backs=0, sub_rounds=0, forwards=0, host_draw_seconds=0.0)
@@ -904,9 +914,14 @@ class KPFCNN(nn.Module):
                 groups.setdefault(width(c), []).append(i)
         for n_extra, members in groups.items():
             self._many_device_loop(clouds, seeds, members, n_extra, S, on_batch, results, info, stats, host_path,
-                                   dict(finish=finish, cap=cap, want=want, n_pool=n_pool, axes=axes, linear=linear, bias=bias, scale=scale), time)
+                                   dict(finish=finish, evaluate=evaluate, return_scores=return_scores, gts=gts, lut=lut, metric=metric, cap=cap, want=want, n_pool=n_pool, axes=axes, linear=linear, bias=bias, scale=scale), time)
         for i in sorted(host_path):
             results[i], info[i] = self._single_cloud_run(clouds[i], seeds[i])
+            results[i] = dict(results[i])                        # (a copy: the single-cloud loop's own result stays whole)
+            if not return_scores:
+                results[i]['predict_scores'] = None
+            if evaluate and gts[i] is not None:
+                metric.add_confusion(score_on_host(results[i], gts[i], lut, cfg.num_classes)['confusion'])
         return results
 
     def _many_device_loop(self, clouds, seeds, members, n_extra, S, on_batch, results, info, stats, host_path, k, time):
@@ -929,7 +944,7 @@ class KPFCNN(nn.Module):
                 feat = None
                 if n_extra:
                     feat = torch.from_numpy(np.ascontiguousarray(data['feat'], dtype=np.float32)).to(dev)
-                return dict(cloud=i, rng=rng, n=n, proj_inds=data['proj_inds'], proj_dev=getattr(data['search_tree'], 'proj_dev', None), have=0, cur=[], batches=0, spheres=0, retries=0,
+                return dict(cloud=i, rng=rng, n=n, proj_inds=data['proj_inds'], proj_dev=getattr(data['search_tree'], 'proj_dev', None), gt=k['gts'][i], have=0, cur=[], batches=0, spheres=0, retries=0,
                             check=False, points=data['search_tree']._pts().contiguous(), possibility=torch.from_numpy(poss).to(dev),
                             label=torch.from_numpy(np.ascontiguousarray(data['label'], dtype=np.int32)).to(dev), feat=feat)
             return None
@@ -937,13 +952,15 @@ class KPFCNN(nn.Module):
         def retired(st, result, possibility):
             results[st['cloud']] = result
             info[st['cloud']] = dict(num_batches=st['batches'], num_spheres=st['spheres'], retries=st['retries'], possibility=possibility)
+            if 'confusion' in result:
+                k['metric'].add_confusion(result['confusion'])
 
         def own_buffers():
             """This loop's two additions to the table's rebuilt buffers: the splits on the device and the candidate lists' room."""
             t.buf.update(splits_dev=torch.from_numpy(t.splits).to(dev), cand=torch.empty(int(t.splits[-1]), dtype=torch.int32, device=dev))
             return t.buf
 
-        t = CloudSlots(S, admit_next, retired, dev, C_, k['finish'])
+        t = CloudSlots(S, admit_next, retired, dev, C_, k['finish'], k['evaluate'], k['return_scores'], k['lut'])
         slots = t.slots
         if not slots:
             return

@@ -18,7 +18,7 @@ from ... import _abi
 from ... import ops
 from . import _randla_pack
 from ._datapath import GpuSearchTree, preprocess_segmentation   # noqa: F401
-from ._multicloud import CloudSlots, PinnedUpload, check_many_args, finish_cloud
+from ._multicloud import CloudSlots, PinnedUpload, check_many_args, eval_labels, finish_cloud, new_metric, score_on_host
 
 
 class SharedMLP(nn.Module):
@@ -684,7 +684,7 @@ class RandLANet(nn.Module):
     # adding num_points floats in order) with a blocking read of the minimum possibility after every patch; the forward runs at
     # batch 1.  A cloud's patches depend only on its own possibilities and its own shuffle draws -- never on a logit -- so C clouds
     # can advance in lock step and each still produces exactly the patch sequence it produces alone (tests/test_emulated_multicloud.py).
-    def inference_many(self, clouds, seeds=None, max_in_flight=16, on_batch=None, finish="device"):
+    def inference_many(self, clouds, seeds=None, max_in_flight=16, on_batch=None, finish="device", evaluate=False, return_scores=True):
         """Segment a list of raw clouds (dicts as ``inference_begin`` takes) with up to ``max_in_flight`` of them advancing in lock
         step: per round ONE argmin + ONE read-back of the minima (the finished test), one batched sampler call
         (``ops.device_patch_batch``), one neighbour pyramid over [A, k, 3], one forward at batch A and one vote update into a
@@ -700,13 +700,23 @@ class RandLANet(nn.Module):
         ``self.inference_many_info[i]`` keeps, per cloud, ``num_patches`` and its final ``possibility`` (numpy float64).
         ``finish``: where a finished cloud's votes become its result.  ``"device"``: one ``ops.vote_project`` and copies on a copy
         stream while the loop goes on; ``"host"``: a blocking read-back, ``np.argmax`` and two gathers on the host with the loop
-        standing still (the A/B baseline).  The results are equal."""
+        standing still (the A/B baseline).  The results are equal.
+        ``evaluate=True``: a cloud whose dict carries ``label`` -- the dataset's label values of the FULL cloud, one per raw point (a
+        wrong length is a ``ValueError`` before any patch runs) -- is scored against it as the reference's ``run_test`` does
+        (filter_valid_label + SemSegMetric.update, with ``cfg.num_classes`` and ``cfg.ignored_label_inds``): its result gains
+        ``'confusion'`` (int64 [C, C], row = truth) and ``'counts'`` (int64 [3]: scored, ignored, outside the label table), and
+        ``self.inference_many_metric`` is a ``SemSegMetric`` holding the sum over the scored clouds.  ``finish="device"`` scores by
+        ``ops.vote_confusion`` with only the matrix copied out, ``finish="host"`` and the single-cloud loop by numpy: same numbers.
+        ``return_scores=False``: ``'predict_scores'`` is None and no score row is written or copied."""
         cfg, dev = self.cfg, self.device
         n_clouds = len(clouds)
         S, seeds = check_many_args("RandLANet.inference_many", self, n_clouds, max_in_flight, seeds,
                                    lambda n: [int(s) for s in self.rng.integers(0, 2 ** 63 - 1, size=n)], finish)
         self.test_smooth = 0.95
         k, C_ = int(cfg.num_points), int(cfg.num_classes)
+        gts = eval_labels("RandLANet.inference_many", clouds, evaluate)
+        lut = ops.label_lut(C_, cfg.get('ignored_label_inds', []) or []) if evaluate else None
+        metric = self.inference_many_metric = new_metric() if evaluate else None
         results = [None] * n_clouds
         info = self.inference_many_info = [None] * n_clouds
         host_path = []
@@ -723,15 +733,17 @@ class RandLANet(nn.Module):
                     host_path.append(i)
                     continue
                 st.update(cloud=i, rng=rng, proj_inds=data['proj_inds'], proj_dev=getattr(data['search_tree'], 'proj_dev', None),
-                          n=int(n), patches=0)
+                          n=int(n), patches=0, gt=gts[i])
                 return st
             return None
 
         def retired(st, result, possibility):
             results[st['cloud']] = result
             info[st['cloud']] = dict(num_patches=st['patches'], possibility=possibility)
+            if 'confusion' in result:
+                metric.add_confusion(result['confusion'])
 
-        t = CloudSlots(S, admit_next, retired, dev, C_, finish)
+        t = CloudSlots(S, admit_next, retired, dev, C_, finish, evaluate, return_scores, lut)
         slots = t.slots
         if slots:
             idx = torch.zeros(len(slots), dtype=torch.int32, device=dev)
@@ -780,7 +792,11 @@ class RandLANet(nn.Module):
                     count += 1
                     if self.inference_end(inp, self(inp['data'])):
                         break
-                results[i] = self.inference_result
+                results[i] = dict(self.inference_result)         # (a copy: the single-cloud loop's own result stays whole)
+                if not return_scores:
+                    results[i]['predict_scores'] = None
+                if evaluate and gts[i] is not None:
+                    metric.add_confusion(score_on_host(results[i], gts[i], lut, C_)['confusion'])
                 st = getattr(self, '_dev_loop', None)
                 info[i] = dict(num_patches=count, possibility=np.array(self.possibility) if st is None else st['possibility'].cpu().numpy())
         finally:
