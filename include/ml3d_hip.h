@@ -595,6 +595,52 @@ int ml3d_iou_bev(const float* boxes_a, const float* boxes_b, int64_t n, int64_t 
 int ml3d_iou_3d(const float* boxes_a, const float* boxes_b, int64_t n, int64_t m, float* out_iou, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* ml3d_det_match: box matching for the detection metric, every frame of a validation split in one call -- precision_3d of      */
+/*   ml3d/metrics/mAP.py:38-135 without its per-frame host loop.  Two launches whatever frames / classes / difficulties are;    */
+/*   nothing is read back inside the call.                                                                                      */
+/* Inputs (device memory), concatenated over `frames` frames:                                                                   */
+/*   pred_box  float [num_pred, 7]  the dict's bbox rows (x, y, z, w, h, l, yaw), y = bottom face (camera frame), finite        */
+/*   pred_cls  int32 [num_pred]     index into `classes`; anything outside [0, num_classes) = a box filter_data drops           */
+/*   pred_dmask uint32 [num_pred]   bit j: the box passes difficulty j (0 <= difficulty <= difficulties[j]; all ones without a   */
+/*                                  `difficulty` entry)                                                                         */
+/*   pred_start int64 [frames + 1]  row splits;  tgt_box / tgt_lab / tgt_dmask / tgt_start: the same for the targets, tgt_lab   */
+/*                                  an id of the caller's vocabulary: 0 .. num_classes - 1 = `classes`, other names >= that,    */
+/*                                  -1 = a target that neither `classes` nor the similar values keep                            */
+/*   pair_start int64 [frames + 1]  pair_start[f] = sum over g < f of P_g * T_g (P_g, T_g = frame g's predictions / targets);    */
+/*                                  num_pairs = pair_start[frames]                                                              */
+/*   min_overlap float [num_classes];  similar int32 [num_classes] = the id of similar_classes.get(classes[c]), or -1          */
+/*   metrics   1 = BEV, 2 = 3-D, 3 = both                                                                                       */
+/* Outputs:                                                                                                                     */
+/*   out_flags uint8 [2, num_difficulties, num_pred]: bit 0 = tp, bit 1 = fp; written for EVERY box (0 where the box is not in  */
+/*             pred_idx).  Plane 0 = BEV, plane 1 = 3-D; a plane that `metrics` does not name is left untouched.                */
+/*   out_fn    int64 [2, num_classes, num_difficulties]: ADDED to (64-bit integer atomics; no float atomics anywhere).           */
+/*   pair_iou  float [2, pair_capacity], the caller's: the kernels' scratch and an output.  SIZE: pair_capacity >= num_pairs =   */
+/*             sum over the frames of P_f * T_f floats PER PLANE, both planes always (there is no *_workspace_bytes call).       */
+/*             Frame f's P_f x T_f block is row-major at pair_start[f] of its plane.  Only pairs whose classes relate are       */
+/*             written -- pred_cls = c with tgt_lab == c or tgt_lab == similar[c] -- with the bits ml3d_iou_bev / ml3d_iou_3d    */
+/*             give on the same boxes (one polygon clip feeds both); every other element is left untouched.                     */
+/* Contract = the reference's code, quirks included.  For frame f and class c: rows = the predictions with pred_cls == c of ALL  */
+/*   difficulties; columns = the targets with tgt_lab == c or == similar[c].  For difficulty j: pred_idx = rows with bit j,     */
+/*   target_idx = columns with tgt_lab == c (NOT the similar ones) and bit j.  Then                                             */
+/*     fp     starts as "every column, similar ones included, has IoU < min_overlap[c]";                                        */
+/*     match  = "some column of target_idx has IoU >= min_overlap[c]"; matched rows get fp = 1;                                 */
+/*     best[t] = the FIRST row of maximal IoU in column t over all rows (an all-zero column elects the class's first            */
+/*              prediction of the frame);                                                                                       */
+/*     a row of pred_idx is tp (and not fp) iff it matches AND is best[t] for some t of target_idx -- not necessarily a t it    */
+/*              matches;                                                                                                        */
+/*     fn[c][j] += the target_idx columns whose IoU with every row is < min_overlap[c]; with pred_idx empty, += |target_idx|.   */
+/*   similar_classes is read with the CLASS as key (mAP.py:98), so dicts keyed by the similar name ({Van: Car}) are inert.     */
+/* frames == 0 or num_pred == 0: returns 0 and does nothing (fn of a split without predictions is the caller's target count).   */
+/* pair_capacity < num_pairs: ML3D_E_WORKSPACE.  num_difficulties outside 1..32, metrics outside 1..3: ML3D_E_INVALID.          */
+/* Non-finite boxes are outside the contract.                                                                                   */
+/* ------------------------------------------------------------------------- */
+int ml3d_det_match(const float* pred_box, const int32_t* pred_cls, const uint32_t* pred_dmask, const int64_t* pred_start,
+                   const float* tgt_box, const int32_t* tgt_lab, const uint32_t* tgt_dmask, const int64_t* tgt_start,
+                   const int64_t* pair_start, int64_t frames, int64_t num_pred, int64_t num_tgt, int64_t num_pairs,
+                   const float* min_overlap, const int32_t* similar, int num_classes, int num_difficulties, int metrics,
+                   uint8_t* out_flags, int64_t* out_fn, float* pair_iou, int64_t pair_capacity, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* patch sampler / vote accumulation                         */
 /* ml3d_nearest_to_center: the k points nearest to a centre — replaces         */
 /*   search_tree.query(center_point, k=num_points) of                          */

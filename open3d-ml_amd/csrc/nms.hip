@@ -185,6 +185,155 @@ iou_pairs(const float* __restrict__ A, const float* __restrict__ B, int64_t n, i
     out[t] = den > 1e-8f ? __fdiv_rn(num, den) : 0.f;
 }
 
+// ---- ml3d_det_match: precision_3d of every frame of a validation split in two launches (ml3d/metrics/mAP.py:38-135) -------------
+// det_pair_iou: one thread per (prediction, target) pair of a frame whose classes relate; box_corners + poly_intersection_area run
+// ONCE and feed both IoUs.  The float32 statements are iou_pairs' in iou_pairs' order, so a pair's two values carry the bits of
+// ml3d_iou_bev / ml3d_iou_3d on the same boxes.  (No circumscribed-circle early-out: the clip of two disjoint boxes is not PROVEN
+// to return an exact 0 in float32, and bit-equality with the two ops is the contract.)
+// A class c relates to a target label l iff l == c or l == similar[c] (>= 0).
+__device__ __forceinline__ bool det_related(int c, int lab, int sim) { return lab == c || (sim >= 0 && lab == sim); }
+
+__global__ void __launch_bounds__(64)
+det_pair_iou(const float* __restrict__ pbox, const int32_t* __restrict__ pcls, const int64_t* __restrict__ pstart,
+             const float* __restrict__ tbox, const int32_t* __restrict__ tlab, const int64_t* __restrict__ tstart,
+             const int64_t* __restrict__ pair_start, int64_t frames, int64_t num_pairs, const int32_t* __restrict__ similar, int C,
+             int metrics, float* __restrict__ pair_iou, int64_t capacity) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= num_pairs) return;
+    int64_t lo = 0, hi = frames;                       // pair_start[lo] <= g < pair_start[hi]: the frame that holds pair g
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (pair_start[mid] <= g) lo = mid; else hi = mid;
+    }
+    const int64_t f = lo, p0 = pstart[f], t0 = tstart[f];
+    const int64_t T = tstart[f + 1] - t0, loc = g - pair_start[f];
+    const int64_t i = p0 + loc / T, j = t0 + loc % T;
+    const int c = pcls[i];
+    if (c < 0 || c >= C || !det_related(c, tlab[j], similar[c])) return;
+    const float* pa = pbox + 7 * i; const float* pb = tbox + 7 * j;
+    float a[5], b[5];
+    center_to_corner_form(pa[0], pa[2], pa[3], pa[5], pa[6], a);           // ground plane of the camera frame: (x, z)
+    center_to_corner_form(pb[0], pb[2], pb[3], pb[5], pb[6], b);
+    P2 ca[4], cb[4];
+    box_corners(a, ca);
+    box_corners(b, cb);
+    const float inter = poly_intersection_area(ca, cb);
+    const float aa = __fmul_rn(__fsub_rn(a[2], a[0]), __fsub_rn(a[3], a[1]));
+    const float ab = __fmul_rn(__fsub_rn(b[2], b[0]), __fsub_rn(b[3], b[1]));
+    if (metrics & 1) {
+        const float den = __fsub_rn(__fadd_rn(aa, ab), inter);
+        pair_iou[g] = den > 1e-8f ? __fdiv_rn(inter, den) : 0.f;
+    }
+    if (metrics & 2) {
+        // y axis points down: the box spans [y - h, y]
+        const float top = fmaxf(__fsub_rn(pa[1], pa[4]), __fsub_rn(pb[1], pb[4])), bot = fminf(pa[1], pb[1]);
+        const float oh = fmaxf(__fsub_rn(bot, top), 0.f);
+        const float num = __fmul_rn(inter, oh);
+        const float den = __fsub_rn(__fadd_rn(__fmul_rn(aa, pa[4]), __fmul_rn(ab, pb[4])), num);
+        pair_iou[capacity + g] = den > 1e-8f ? __fdiv_rn(num, den) : 0.f;
+    }
+}
+
+// det_match_reduce: one wave per (frame f, class c), the IoU block read from pair_iou in global memory (no LDS, so no cap on a
+// frame's size and nothing for the rule of DESIGN.md section 9.10 to bite on; every loop's trip count is uniform over the wave).
+// Per requested metric, three passes with a barrier between them; the flag bytes of the class's rows are the passes' scratch:
+//   rows     lane = a prediction of class c: over the related columns, fp0 = "every IoU < overlap" and the set of difficulties j
+//            in which a column of target_idx(j) reaches the overlap.  Byte [j][row] <- 4 (matches) | 2 (fp0) | 0, 0 outside pred_idx(j).
+//   columns  lane = a target of label c: over ALL the class's rows, the first row of maximal IoU and "some row reaches the
+//            overlap".  For every j of the column: byte [j][best] 4 -> 5 (lanes that meet on a byte store the same value), and the
+//            column counts in fn[c][j] when no row reaches it, or unconditionally while pred_idx(j) is empty.
+//   rows     4 -> 2 (matched, but nobody's best: fp), 5 -> 1 (tp).
+// Flags and counts are pure functions of the inputs; fn is ADDED to with 64-bit integer atomics.
+__global__ void __launch_bounds__(64)
+det_match_reduce(const int32_t* __restrict__ pcls, const uint32_t* __restrict__ pdm, const int64_t* __restrict__ pstart,
+                 const int32_t* __restrict__ tlab, const uint32_t* __restrict__ tdm, const int64_t* __restrict__ tstart,
+                 const int64_t* __restrict__ pair_start, int64_t num_pred, const float* __restrict__ min_overlap,
+                 const int32_t* __restrict__ similar, int C, int D, int metrics, uint8_t* flags,
+                 int64_t* __restrict__ out_fn, const float* __restrict__ pair_iou, int64_t capacity) {
+    const int64_t f = blockIdx.x / C;
+    const int c = (int)(blockIdx.x - f * C), lane = threadIdx.x;
+    const int64_t p0 = pstart[f], t0 = tstart[f];
+    const int P = (int)(pstart[f + 1] - p0), T = (int)(tstart[f + 1] - t0);
+    const float mo = min_overlap[c];
+    const int sim = similar[c];
+    const uint32_t dall = D >= 32 ? 0xffffffffu : ((1u << D) - 1u);
+    const int rounds_p = (P + 63) >> 6, rounds_t = (T + 63) >> 6;
+    for (int m = 0; m < 2; ++m) {
+        if (!((metrics >> m) & 1)) continue;
+        const float* iou = pair_iou + (int64_t)m * capacity + pair_start[f];
+        uint8_t* fl = flags + (int64_t)m * D * num_pred;
+        // ---- rows
+        uint32_t have = 0;                             // difficulties whose pred_idx is not empty
+        for (int r = 0; r < rounds_p; ++r) {
+            const int p = r * 64 + lane;
+            const int cls = p < P ? pcls[p0 + p] : -2;
+            const bool mine = cls == c;
+            const uint32_t pm = mine ? (pdm[p0 + p] & dall) : 0u;
+            bool fp0 = true;
+            uint32_t match = 0;
+            for (int t = 0; t < T; ++t) {              // (uniform trip count; the loads are global)
+                const int lab = tlab[t0 + t];
+                if (mine && det_related(c, lab, sim)) {
+                    const float v = iou[(int64_t)p * T + t];
+                    if (!(v < mo)) fp0 = false;
+                    if (v >= mo && lab == c) match |= tdm[t0 + t];
+                }
+            }
+            have |= pm;
+            if (mine || (c == 0 && p < P && (cls < 0 || cls >= C))) {      // (boxes of no class: zeros, written by class 0's wave)
+                for (int j = 0; j < D; ++j) {
+                    const bool in = (pm >> j) & 1u;
+                    fl[(int64_t)j * num_pred + p0 + p] = !in ? 0 : ((match >> j) & 1u) ? 4 : fp0 ? 2 : 0;
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) have |= __shfl_xor(have, s);
+        __syncthreads();
+        // ---- columns
+        int64_t miss = 0;                              // lane j: fn[c][j] of this frame
+        for (int r = 0; r < rounds_t; ++r) {
+            const int t = r * 64 + lane;
+            const bool mine = t < T && tlab[t0 + t] == c;
+            const uint32_t tm = mine ? (tdm[t0 + t] & dall) : 0u;
+            float bestv = 0.f;
+            int best = -1;
+            bool reached = false;
+            for (int p = 0; p < P; ++p) {
+                if (mine && pcls[p0 + p] == c) {
+                    const float v = iou[(int64_t)p * T + t];
+                    if (best < 0 || v > bestv) { best = p; bestv = v; }     // the FIRST row of maximal IoU
+                    if (v >= mo) reached = true;
+                }
+            }
+            for (int j = 0; j < D; ++j) {
+                const bool in = (tm >> j) & 1u;
+                if (in && best >= 0) {
+                    uint8_t* cell = fl + (int64_t)j * num_pred + p0 + best;
+                    if (*cell & 4) *cell = 5;
+                }
+                const bool counts = in && (!((have >> j) & 1u) || !reached);
+                const u64 bal = __ballot(counts);
+                if (lane == j) miss += __popcll(bal);
+            }
+        }
+        if (lane < D && miss) atomicAdd((unsigned long long*)(out_fn + ((int64_t)m * C + c) * D + lane), (unsigned long long)miss);
+        __syncthreads();
+        // ---- rows again
+        for (int r = 0; r < rounds_p; ++r) {
+            const int p = r * 64 + lane;
+            if (p < P && pcls[p0 + p] == c) {
+                for (int j = 0; j < D; ++j) {
+                    uint8_t* cell = fl + (int64_t)j * num_pred + p0 + p;
+                    const uint8_t v = *cell;
+                    if (v & 4) *cell = (v & 1) ? 1 : 2;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
 // key = ~ordered(score) << 32 | index : ascending key == descending score, ties by ascending index
 __global__ void nms_keys(const float* __restrict__ scores, int64_t n, u64* __restrict__ keys, uint32_t* __restrict__ vals) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -775,5 +924,32 @@ extern "C" int ml3d_iou_3d(const float* boxes_a, const float* boxes_b, int64_t n
     if (!boxes_a || !boxes_b || !out_iou) return ML3D_E_INVALID;
     hipLaunchKernelGGL(ml3d::iou_pairs, dim3((unsigned)((n * m + 63) / 64)), dim3(64), 0, (hipStream_t)stream, boxes_a, boxes_b,
                        n, m, 1, out_iou);
+    return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
+}
+
+extern "C" int ml3d_det_match(const float* pred_box, const int32_t* pred_cls, const uint32_t* pred_dmask, const int64_t* pred_start,
+                              const float* tgt_box, const int32_t* tgt_lab, const uint32_t* tgt_dmask, const int64_t* tgt_start,
+                              const int64_t* pair_start, int64_t frames, int64_t num_pred, int64_t num_tgt, int64_t num_pairs,
+                              const float* min_overlap, const int32_t* similar, int num_classes, int num_difficulties, int metrics,
+                              uint8_t* out_flags, int64_t* out_fn, float* pair_iou, int64_t pair_capacity, void* stream) {
+    if (frames < 0 || num_pred < 0 || num_tgt < 0 || num_pairs < 0 || num_classes < 1 || num_difficulties < 1 || num_difficulties > 32 ||
+        metrics < 1 || metrics > 3)
+        return ML3D_E_INVALID;
+    if (frames * (int64_t)num_classes > 0x7fffffffll || num_pred > 0x7fffffffll || num_tgt > 0x7fffffffll || (num_pairs + 63) / 64 > 0x7fffffffll)
+        return ML3D_E_UNSUPPORTED;
+    if (pair_capacity < num_pairs) return ML3D_E_WORKSPACE;
+    if (frames == 0 || num_pred == 0) return 0;
+    if (!pred_box || !pred_cls || !pred_dmask || !pred_start || !tgt_start || !pair_start || !min_overlap || !similar || !out_flags || !out_fn ||
+        (num_tgt > 0 && (!tgt_box || !tgt_lab || !tgt_dmask)) || (num_pairs > 0 && !pair_iou))
+        return ML3D_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (num_pairs > 0) {
+        hipLaunchKernelGGL(ml3d::det_pair_iou, dim3((unsigned)((num_pairs + 63) / 64)), dim3(64), 0, st, pred_box, pred_cls, pred_start, tgt_box,
+                           tgt_lab, tgt_start, pair_start, frames, num_pairs, similar, num_classes, metrics, pair_iou, pair_capacity);
+        if (hipGetLastError() != hipSuccess) return ML3D_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(ml3d::det_match_reduce, dim3((unsigned)(frames * num_classes)), dim3(64), 0, st, pred_cls, pred_dmask, pred_start, tgt_lab,
+                       tgt_dmask, tgt_start, pair_start, num_pred, min_overlap, similar, num_classes, num_difficulties, metrics, out_flags,
+                       out_fn, pair_iou, pair_capacity);
     return hipGetLastError() == hipSuccess ? 0 : ML3D_E_LAUNCH;
 }

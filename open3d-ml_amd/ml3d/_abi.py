@@ -68,6 +68,7 @@ SYMBOLS = [
     "ml3d_pp_boxes",
     "ml3d_iou_bev",
     "ml3d_iou_3d",
+    "ml3d_det_match",
     "ml3d_nearest_to_center_workspace_bytes",
     "ml3d_nearest_to_center",
     "ml3d_nearest_to_center_dev",
@@ -243,6 +244,8 @@ def bind(lib):
     lib.ml3d_iou_bev.argtypes = [vp, vp, i64, i64, vp, vp]
     lib.ml3d_iou_3d.restype = C.c_int
     lib.ml3d_iou_3d.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.ml3d_det_match.restype = C.c_int
+    lib.ml3d_det_match.argtypes = [vp] * 9 + [i64] * 4 + [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, i64, vp]
     lib.ml3d_nearest_to_center_workspace_bytes.restype = sz
     lib.ml3d_nearest_to_center_workspace_bytes.argtypes = [i64]
     lib.ml3d_nearest_to_center.restype = C.c_int

@@ -16,7 +16,7 @@ from .voxel import (voxelize, subsample_batch, subsample, rotate_points, grid_su
 from .kpconv import (kpconv_rigid, kpconv_deformable, linear, gather_pool, kpconv_weighted, kpconv_weighted_backward,   # noqa: F401
                      KPConvFunction)
 from .detection import (pillar_features, conv2d_nhwc, pack_bf16x3, linear_bf16x3, deconv2d_nhwc, nhwc_to_nchw, nms, pointpillars_boxes,   # noqa: F401
-                        iou_bev, iou_3d, topk_rows)
+                        iou_bev, iou_3d, topk_rows, det_match, det_pair_starts)
 from .sampler import (nearest_to_center, argmax_labels, vote_update, vote_project, device_patch, possibility_argmin,   # noqa: F401
                       device_patch_batch, sphere_select, device_sphere_batch, label_lut, vote_confusion, score_confusion)
 from .train import (gemm_tn, LinearFunction, BatchNormActFunction, batch_norm_act, GatherRowsFunction, GatherPoolFunction,   # noqa: F401

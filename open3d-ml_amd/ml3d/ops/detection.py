@@ -249,3 +249,78 @@ def iou_3d(boxes_a, boxes_b):
     """``open3d.ml.contrib.iou_3d_*`` (ml3d/metrics/mAP.py:87): 3-D IoU of every pair; boxes [N, 7] / [M, 7] =
     (x, y, z, w, h, l, yaw) with y the bottom face (camera frame, y down) -> float32 [N, M]."""
     return _iou("ml3d_iou_3d", boxes_a, boxes_b, 7)
+
+
+def det_pair_starts(pred_start, tgt_start):
+    """int64 [F + 1]: frame f's IoU block starts at ``sum(P_g * T_g for g < f)`` of a ``pair_iou`` plane (host arrays in and out)."""
+    ps, ts = np.asarray(pred_start, np.int64), np.asarray(tgt_start, np.int64)
+    out = np.zeros(ps.size, np.int64)
+    np.cumsum(np.diff(ps) * np.diff(ts), out=out[1:])
+    return out
+
+
+def det_match(pred_box, pred_cls, pred_dmask, pred_start, tgt_box, tgt_lab, tgt_dmask, tgt_start, min_overlap, similar,
+              num_difficulties, metrics=3, out_flags=None, out_fn=None, return_iou=False, pair_start=None, num_pairs=None,
+              pair_iou=None):
+    """``precision_3d`` (ml3d/metrics/mAP.py:38-135) for every frame of a split in ONE call of ``ml3d_det_match`` (two launches,
+    no read-back): device tensors ``pred_box`` float32 [NP, 7], ``pred_cls`` int32 [NP] (index into ``classes``, -1 = dropped),
+    ``pred_dmask`` int32 [NP] (bit j: passes difficulty j), the same for the targets (``tgt_lab``: vocabulary ids),
+    ``min_overlap`` float32 [C], ``similar`` int32 [C].  ``pred_start`` / ``tgt_start`` are the int64 [F + 1] row splits: HOST
+    arrays, from which the block offsets are computed and uploaded here -- or device tensors together with ``pair_start`` (device,
+    ``det_pair_starts``) and ``num_pairs``, for a caller that uploaded everything at once.
+    Returns (``flags`` uint8 [2, D, NP]: bit 0 tp, bit 1 fp, plane 0 BEV / 1 3-D, a plane ``metrics`` (1 | 2 | 3) does not name
+    untouched; ``fn`` int64 [2, C, D], ADDED to when handed in) and, with ``return_iou=True``, ``pair_iou`` float32
+    [2, num_pairs]: frame f's P_f x T_f block row-major at its offset, only the pairs whose classes relate written
+    (``pair_iou=``: the caller's buffer, float32 [2, capacity]; a capacity below ``num_pairs`` is refused: "workspace too small")."""
+    lib = _abi.get()
+    _need_gpu(pred_box, pred_cls, pred_dmask, tgt_box, tgt_lab, tgt_dmask, min_overlap, similar)
+    dev = pred_box.device
+    D, C_ = int(num_difficulties), int(min_overlap.numel())
+    NP, NT = int(pred_cls.numel()), int(tgt_lab.numel())
+
+    def bad(why):
+        raise RuntimeError("det_match: invalid argument: " + why)
+    for t, dt, shape, name in ((pred_box, torch.float32, (NP, 7), "pred_box"), (tgt_box, torch.float32, (NT, 7), "tgt_box"),
+                               (pred_cls, torch.int32, (NP,), "pred_cls"), (tgt_lab, torch.int32, (NT,), "tgt_lab"),
+                               (pred_dmask, torch.int32, (NP,), "pred_dmask"), (tgt_dmask, torch.int32, (NT,), "tgt_dmask"),
+                               (min_overlap, torch.float32, (C_,), "min_overlap"), (similar, torch.int32, (C_,), "similar")):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            bad("%s must be a contiguous %s tensor of shape %s" % (name, dt, list(shape)))
+    if not 1 <= D <= 32 or C_ < 1 or int(metrics) not in (1, 2, 3):
+        bad("1..32 difficulties, at least one class and metrics 1, 2 or 3 expected")
+    if pair_start is None:
+        ps = np.ascontiguousarray(pred_start.cpu().numpy() if isinstance(pred_start, torch.Tensor) else pred_start, dtype=np.int64)
+        ts = np.ascontiguousarray(tgt_start.cpu().numpy() if isinstance(tgt_start, torch.Tensor) else tgt_start, dtype=np.int64)
+        if ps.ndim != 1 or ps.shape != ts.shape or ps.size < 1 or ps[0] != 0 or ts[0] != 0 or ps[-1] != NP or ts[-1] != NT or \
+                (np.diff(ps) < 0).any() or (np.diff(ts) < 0).any():
+            bad("pred_start / tgt_start must be row splits [F + 1] of the predictions / targets")
+        starts = np.stack([ps, ts, det_pair_starts(ps, ts)])
+        num_pairs = int(starts[2, -1])
+        pred_start, tgt_start, pair_start = torch.from_numpy(starts).to(dev)
+    else:
+        _need_gpu(pred_start, tgt_start, pair_start)
+        for t in (pred_start, tgt_start, pair_start):
+            if t.dtype != torch.int64 or t.dim() != 1 or t.shape != pred_start.shape or not t.is_contiguous() or t.numel() < 1:
+                bad("the three row splits must be contiguous int64 [F + 1]")
+        if num_pairs is None:
+            bad("num_pairs goes with pair_start")
+    F = int(pred_start.numel()) - 1
+    if out_flags is None:
+        out_flags = torch.zeros((2, D, NP), dtype=torch.uint8, device=dev)
+    elif out_flags.dtype != torch.uint8 or tuple(out_flags.shape) != (2, D, NP) or not out_flags.is_contiguous():
+        bad("out_flags must be contiguous uint8 [2, D, NP]")
+    if out_fn is None:
+        out_fn = torch.zeros((2, C_, D), dtype=torch.int64, device=dev)
+    elif out_fn.dtype != torch.int64 or tuple(out_fn.shape) != (2, C_, D) or not out_fn.is_contiguous():
+        bad("out_fn must be contiguous int64 [2, C, D]")
+    if pair_iou is None:
+        pair_iou = torch.empty((2, int(num_pairs)), dtype=torch.float32, device=dev)
+    elif pair_iou.dtype != torch.float32 or pair_iou.dim() != 2 or pair_iou.shape[0] != 2 or not pair_iou.is_contiguous():
+        bad("pair_iou must be contiguous float32 [2, capacity]")
+    with torch.cuda.device(dev):
+        rc = lib.ml3d_det_match(pred_box.data_ptr(), pred_cls.data_ptr(), pred_dmask.data_ptr(), pred_start.data_ptr(),
+                                tgt_box.data_ptr(), tgt_lab.data_ptr(), tgt_dmask.data_ptr(), tgt_start.data_ptr(),
+                                pair_start.data_ptr(), F, NP, NT, int(num_pairs), min_overlap.data_ptr(), similar.data_ptr(), C_, D,
+                                int(metrics), out_flags.data_ptr(), out_fn.data_ptr(), pair_iou.data_ptr(), int(pair_iou.shape[1]), _stream())
+    _abi.check(rc, "ml3d_det_match")
+    return (out_flags, out_fn, pair_iou) if return_iou else (out_flags, out_fn)

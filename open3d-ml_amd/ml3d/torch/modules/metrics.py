@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from ... import ops
+from ...metrics.mAP import ObjdetMetric   # noqa: F401  (the detection counterpart, scored by ops.det_match)
 
 
 def host_confusion(pred, gt, lut, num_classes):

@@ -4,7 +4,9 @@ re-exports it — with ONE change: the three inference hot-path models (``RandLA
 ``PointTransformer``, ``PVCNN`` and ``SparseConvUnet`` extensions of this repository are registered over the checkout's in ``ml3d.utils``'s MODEL registry, so
 ``get_module("model", "RandLANet", "torch")`` (``scripts/run_pipeline.py:129-132``) returns the MI355X-native class.
 Set ``ML3D_AMD_KEEP_REFERENCE_MODELS=1`` to leave the registry alone (the reference's PyTorch forwards then run on the
-native ops only)."""
+native ops only).  Likewise ``mAP`` -- in the checkout's ``ml3d.metrics`` and in ``ml3d.torch.pipelines.object_detection``, the
+two names ``run_valid`` reaches it by -- is rebound to this repository's ``ml3d.metrics.mAP``, which matches every frame in one
+``ml3d_det_match`` call; ``ML3D_AMD_KEEP_REFERENCE_METRICS=1`` leaves both alone.  No other name is touched."""
 import os as _os
 
 from . import layers   # noqa: F401
@@ -55,3 +57,16 @@ if _checkout():
 
     if _os.environ.get("ML3D_AMD_KEEP_REFERENCE_MODELS", "0") != "1":
         _register_native_models()
+
+    def _rebind_native_metrics():
+        import importlib
+        import ml3d.metrics as _metrics
+        import ml3d.torch.pipelines.object_detection as _objdet
+        from ... import _product
+        _product.product()
+        native = importlib.import_module("ml3d_amd.metrics")
+        _metrics.mAP = native.mAP
+        _objdet.mAP = native.mAP
+
+    if _os.environ.get("ML3D_AMD_KEEP_REFERENCE_METRICS", "0") != "1":
+        _rebind_native_metrics()
